@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- batched LZMA / LZMA2 decode throughput on MI355X (the BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: it makes the headline's corpus, uploads it, runs W warm-up and
+exactly K timed steps, checks every stream's status and length, writes DIR/*.npy when --dump-outputs is given and
+prints the result line (`ms_per_step` = wall milliseconds of one timed step).  `--full` adds everything described
+below that is not the headline: the side configs, the extras (host-to-host legs, stream-count sweep, .xz container,
+lone-wave launches, shard projection), the CPU baselines and the SHA-256 comparison of every decoded byte with the
+plaintext.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's shard): status.npy and out_len.npy (float64,
+one entry per stream) and decoded_sample.npy (float32 bytes of a fixed, seeded sample of the streams, with
+decoded_sample_streams.npy / decoded_sample_offsets.npy saying which bytes they are), under 64 MB in all.  The
+corpus depends only on the arguments, so two builds can be compared output for output.
 
 A "step" is one pass of the hot path (the gfx950 decode kernel) over one batch of synthetic
 compressed streams that is already resident in HBM.
@@ -252,12 +264,62 @@ def median(xs):
     return None if n == 0 else xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
 
 
-def verify_all(batch, n, osz, digests, tag):
+def check_results(batch, n, osz, tag):
+    """every stream decoded without error to its full length (the plain run's check; verify_all adds the bytes)"""
     res = batch.results()
     bad = [i for i in range(n) if res[i][1] != 0 or res[i][0] != osz]
     if bad:
         raise SystemExit("%s: %d streams failed to decode (first: %d, status %d, out_len %d)"
                          % (tag, len(bad), bad[0], res[bad[0]][1], res[bad[0]][0]))
+
+
+DUMP_SEED = 20261016
+DUMP_STREAMS = 128          # streams in decoded_sample.npy (all of them when the batch has fewer)
+DUMP_ELEMS = 12 << 20       # float32 elements of decoded_sample.npy: 48 MiB, the rest of 64 MB is per-stream arrays
+DUMP_BLOCK = 4096           # a stream longer than its share of DUMP_ELEMS is sampled in blocks of this many bytes
+
+
+def dump_plan(n, osz):
+    """-> (stream indices, byte offsets of the blocks taken from each, block length): the fixed, seeded sample of
+    --dump-outputs.  Depends only on (n, osz), so that runs with the same arguments dump the same bytes."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    streams = np.arange(n) if n <= DUMP_STREAMS else np.sort(rng.choice(n, DUMP_STREAMS, replace=False))
+    per = DUMP_ELEMS // len(streams)
+    if osz <= per:
+        return streams, np.zeros(1, dtype=np.int64), osz
+    blocks = osz // DUMP_BLOCK
+    k = max(1, min(blocks, per // DUMP_BLOCK))
+    return streams, np.sort(rng.choice(blocks, k, replace=False)).astype(np.int64) * DUMP_BLOCK, DUMP_BLOCK
+
+
+def dump_outputs(batch, n, osz, stream_ids, out_dir):
+    """what a caller of the timed path receives, as float arrays: status and out_len of every stream, the bytes of
+    the sample of dump_plan (bytes past a stream's out_len are 0)"""
+    import numpy as np
+    res = batch.results()
+    status = np.array([r[1] for r in res[:n]], dtype=np.float64)
+    out_len = np.array([r[0] for r in res[:n]], dtype=np.float64)
+    streams, offsets, blk = dump_plan(n, osz)
+    sample = np.zeros((len(streams), len(offsets) * blk), dtype=np.float32)
+    for row, i in enumerate(streams):
+        valid = int(min(res[i][0], osz))
+        data = np.frombuffer(batch.download(int(i), valid), dtype=np.uint8) if valid else np.zeros(0, np.uint8)
+        full = np.zeros(osz, dtype=np.uint8)
+        full[:valid] = data
+        sample[row] = np.concatenate([full[o:o + blk] for o in offsets])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"status": status, "out_len": out_len, "decoded_sample": sample,
+              "decoded_sample_streams": np.asarray(stream_ids, dtype=np.float64)[streams],
+              "decoded_sample_offsets": offsets.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("[dump] %d streams' status / out_len, %d x %d decoded bytes -> %s (%.1f MB)"
+        % (n, sample.shape[0], sample.shape[1], out_dir, sum(a.nbytes for a in arrays.values()) / 1e6))
+
+
+def verify_all(batch, n, osz, digests, tag):
+    check_results(batch, n, osz, tag)
     t0 = time.time()
 
     def check(i):
@@ -594,10 +656,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: side configs, extras, CPU baselines and the SHA-256 check of every decoded byte")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--side-steps", type=int, default=3, help="timed steps of each entry of `configs` (1 warm-up)")
-    ap.add_argument("--configs", default="all",
-                    help="N=1: comma list of side configs to run (%s), 'all' (= %s) or 'none'" % (",".join(SIDE_ALL), ",".join(SIDE)))
-    ap.add_argument("--extras", default="all", help="N=1: comma list of %s, 'all' or 'none'" % ",".join(EXTRAS))
+    ap.add_argument("--configs", default=None,
+                    help="--full, N=1: comma list of side configs to run (%s), 'all' (= %s, the default) or 'none'"
+                         % (",".join(SIDE_ALL), ",".join(SIDE)))
+    ap.add_argument("--extras", default=None, help="--full, N=1: comma list of %s, 'all' (the default) or 'none'" % ",".join(EXTRAS))
     ap.add_argument("--headline", default="cfg3", choices=list(CONFIGS),
                     help="the ONE workload reported as `value` at every N (cfg3; cfg3-heavy for big nodes; any other "
                          "config for profiling runs)")
@@ -612,6 +679,10 @@ def main():
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where rank 0 writes the full record (every config's roofline.issue, host_to_host, sweep, containers, library)")
     args = ap.parse_args()
+    if not args.full:
+        for opt, v in (("--configs", args.configs), ("--extras", args.extras)):
+            if v not in (None, "none"):
+                raise SystemExit("bench.py: %s %s needs --full (a plain run measures the headline alone)" % (opt, v))
     if os.environ.get("XLZ_SO") and not args.allow_xlz_so:
         raise SystemExit("bench.py: XLZ_SO is set (%s): the numbers would belong to another library than the tree's; "
                          "pass --allow-xlz-so for an A/B run" % os.environ["XLZ_SO"])
@@ -630,10 +701,11 @@ def main():
                 v["streams"] = max(8, int(v["streams"] * args.scale))
     head = args.headline
     side, extras = [], []
-    if world == 1:  # the side configs, the sweep and the host-to-host legs are single-GPU measurements
-        side = [] if args.configs == "none" else SIDE if args.configs == "all" else [c for c in args.configs.split(",") if c]
+    if world == 1 and args.full:  # the side configs, the sweep and the host-to-host legs are single-GPU measurements
+        configs, extras_arg = args.configs or "all", args.extras or "all"
+        side = [] if configs == "none" else SIDE if configs == "all" else [c for c in configs.split(",") if c]
         side = [c for c in side if c != head]
-        extras = [] if args.extras == "none" else EXTRAS if args.extras == "all" else [e for e in args.extras.split(",") if e]
+        extras = [] if extras_arg == "none" else EXTRAS if extras_arg == "all" else [e for e in extras_arg.split(",") if e]
     if ("h2h" in extras or "sweep" in extras) and "cfg2-T" not in side and head != "cfg2-T":
         side.append("cfg2-T")   # (their corpus)
     names = [head] + side
@@ -641,7 +713,8 @@ def main():
     # ---- synthetic corpora.  The pool's workers are ALL forked here, before anything touches the GPU (a process that has
     # initialised HIP must not fork); jobs can be handed to them at any time afterwards.
     ncpu = effective_cpus()
-    workers = max(1, min((os.cpu_count() or 1) // max(1, min(world, 8)), 64))
+    # sized by the CPUs this process may use, not by the host's count: more workers than CPUs only compete
+    workers = max(1, min(ncpu // max(1, min(world, 8)), 64))
     pool = ProcessPoolExecutor(max_workers=workers)
     pids = set(pool.map(_warm, range(workers)))   # the first submit forks the workers (fork context: all of them at once)
     log("[rank %d] %d corpus workers forked (%d host CPUs usable)" % (rank, len(pids), ncpu))
@@ -710,10 +783,7 @@ def main():
         return xz_done[0]
 
     t_gen0 = time.time()
-    get(head)
-    gen_head_s = time.time() - t_gen0
-    for name in side[:2]:   # compressed while torch is imported, HIP initialised and the headline uploaded
-        start(name)
+    start(head)   # compressed by the workers while torch is imported and HIP initialised (the workers are forked already)
 
     import torch
     import torch.distributed as dist
@@ -740,6 +810,10 @@ def main():
                          % (lib_info["path"], lib_info["build_id"], lib_info["tree_source_id"]))
     ctx = lzma_amd.Context(local_rank)
     red_dev = "cuda" if backend == "nccl" else "cpu"
+    get(head)
+    gen_head_s = time.time() - t_gen0
+    for name in side[:2]:   # compressed while the headline is uploaded
+        start(name)
 
     def barrier():
         multigpu.barrier(dist, torch.cuda.synchronize)
@@ -763,7 +837,7 @@ def main():
                 "unit_ms_median": round(float(np.median(dur)) * 1e3, 3),
                 "source": "live: a launch of the config's first %d units alone (one wave each, the rest of the chip idle)" % len(dur)}
 
-    def gpu_leg(name, steps, warmup, with_lone=True, quiet_host=False):
+    def gpu_leg(name, steps, warmup, with_lone=True, quiet_host=False, dump_dir="", stream_ids=None):
         spec = specs[name]
         comp, dig = get(name)
         osz = out_size_of(spec)
@@ -773,7 +847,12 @@ def main():
         if quiet_host:
             drain()
         t_local, kernel_ms, each = timed_steps(ctx, batch, steps, warmup, torch.cuda.synchronize, barrier if world > 1 else None)
-        verify_all(batch, len(comp), osz, dig, "rank %d %s" % (rank, name))
+        if dump_dir:
+            dump_outputs(batch, len(comp), osz, stream_ids if stream_ids is not None else range(len(comp)), dump_dir)
+        if args.full:
+            verify_all(batch, len(comp), osz, dig, "rank %d %s" % (rank, name))
+        else:
+            check_results(batch, len(comp), osz, "rank %d %s" % (rank, name))
         cin, cout, units = batch.stats()
         occ = occupancy(batch, kernel_ms)
         if args.trace_out:
@@ -785,7 +864,7 @@ def main():
         return t_local, kernel_ms, cin, cout, units, occ, lone, each
 
     def cpu_leg(name, target_s):
-        if args.no_cpu_baseline or rank != 0 or world != 1:   # contract: rank 0 at N = 1 only
+        if not args.full or args.no_cpu_baseline or rank != 0 or world != 1:   # contract: rank 0 at N = 1 only
             return None
         spec = specs[name]
         comp, dig = corp[name]
@@ -849,7 +928,11 @@ def main():
     # ------------------------------------------------------------ the headline: one workload at every N ----
     spec = specs[head]
     t_head0 = time.time()
-    t_local, kernel_ms, cin, cout, units, occ, lone, each = gpu_leg(head, args.steps, args.warmup, quiet_host=True)
+    # the stream ids of this rank's shard (what start() made; N = 1: all of them), for the dump's sample
+    head_ids = multigpu.partition_by_weight([out_size_of(spec)] * spec["streams"], world)[rank]
+    t_local, kernel_ms, cin, cout, units, occ, lone, each = gpu_leg(head, args.steps, args.warmup, quiet_host=True,
+                                                                    dump_dir=args.dump_outputs if rank == 0 else "",
+                                                                    stream_ids=head_ids)
     for name in side[2:]:   # the rest of the corpora: compressed while the side legs run (their launches are timed by HIP events)
         start(name)
     xz_start()
@@ -1018,8 +1101,9 @@ def main():
         t0 = time.perf_counter()
         n_out = 0
         while pos < len(xz[0]) and nblk < 128:
-            n_out += len(dec.decompress(xz[0][pos:pos + (1 << 20)]))
-            pos += 1 << 20
+            piece = xz[0][pos:pos + (1 << 20)]   # (shorter at the end of the file: a --scale run reaches it)
+            n_out += len(dec.decompress(piece))
+            pos += len(piece)
             if dec.eof:
                 rest = dec.unused_data
                 pos -= len(rest)
@@ -1047,7 +1131,8 @@ def main():
             "config": {"workload": workload_text(head, spec, per_gpu=False) + "; ONE seeded batch split by stream over %d GPU%s"
                        % (world, "" if world == 1 else "s"),
                        "streams_total": total_streams, "streams_largest_shard": int(n_max),
-                       "bytes_per_stream": out_size_of(spec), "compression_ratio": round(sums[1] / sums[2], 4), "bit_exact": "all",
+                       "bytes_per_stream": out_size_of(spec), "compression_ratio": round(sums[1] / sums[2], 4),
+                       "bit_exact": "all" if args.full else "not checked: status and length of every stream (--full: every byte)",
                        "parallelism": "one batch sharded by stream x%d (partition_by_weight), no collective" % world,
                        "corpus_generation_s": round(gen_s, 1), "kernel_rev": lib_info["kernel_id"], "library": lib_info},
             "roofline": head_res["roofline"],

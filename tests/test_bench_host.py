@@ -180,3 +180,62 @@ def test_corpora_can_be_started_early_and_collected_later():
     assert len(ca) == 6 and len(cb) == 1
     assert hashlib.sha256(lzma.decompress(ca[3], format=lzma.FORMAT_ALONE)).digest() == da[3]
     assert bench.median([3.0, 1.0, 2.0]) == 2.0 and bench.median([4.0, 1.0, 2.0, 3.0]) == 2.5 and bench.median([]) is None
+
+
+class _FakeBatch:
+    """results() / download() of a decoded batch, as lzma_amd.Batch returns them"""
+
+    def __init__(self, outs, cap):
+        self.outs, self.cap = outs, cap
+
+    def results(self):
+        return [(len(o), 0 if len(o) == self.cap else 1, 0) for o in self.outs]
+
+    def download(self, i, length):
+        return self.outs[i][:length]
+
+
+def test_dump_sample_is_fixed_and_under_64_mb():
+    """--dump-outputs: the same (n, out size) dumps the same bytes; every headline's dump stays under 64 MB"""
+    import numpy as np
+    for name, spec in bench.CONFIGS.items():
+        n = spec["streams"]
+        osz = bench.out_size_of(spec)
+        streams, offsets, blk = bench.dump_plan(n, osz)
+        s2, o2, b2 = bench.dump_plan(n, osz)
+        assert np.array_equal(streams, s2) and np.array_equal(offsets, o2) and blk == b2
+        assert len(set(streams.tolist())) == len(streams) == min(n, bench.DUMP_STREAMS)
+        assert 0 <= streams.min() and streams.max() < n
+        assert offsets.min() >= 0 and offsets.max() + blk <= osz
+        total = len(streams) * len(offsets) * blk * 4 + 2 * n * 8 + len(streams) * 8 + len(offsets) * 8
+        assert total < 64e6, (name, total)
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    import numpy as np
+    cap = 5000
+    outs = [bytes([(i * 7 + k) % 256 for k in range(cap)]) for i in range(200)]
+    outs[3] = outs[3][:100]   # a stream that stopped early: its bytes past out_len are dumped as 0
+    ids = list(range(1000, 1200))
+    bench.dump_outputs(_FakeBatch(outs, cap), len(outs), cap, ids, str(tmp_path))
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert set(got) == {"status", "out_len", "decoded_sample", "decoded_sample_streams", "decoded_sample_offsets"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["out_len"].tolist() == [len(o) for o in outs] and got["status"][3] == 1 and got["status"].sum() == 1
+    streams, _, _ = bench.dump_plan(len(outs), cap)
+    assert got["decoded_sample_streams"].tolist() == [ids[i] for i in streams]
+    for row, i in enumerate(streams):
+        want = np.zeros(cap, dtype=np.float32)
+        want[:len(outs[i])] = np.frombuffer(outs[i], dtype=np.uint8)
+        assert np.array_equal(got["decoded_sample"][row], want)
+
+
+def test_side_configs_and_extras_need_full():
+    """a plain run measures the headline alone: asking it for a side config is an error, not a silent no-op"""
+    import os
+    import subprocess
+    import sys
+    for extra in (["--configs", "cfg2-T"], ["--extras", "h2h"]):
+        r = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), "bench.py")] + extra,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and "needs --full" in r.stderr, r.stderr

@@ -13,7 +13,7 @@ TAG=${1:-r04all}
 SIDE=${2:-cfg2-T,cfg2-R,cfg4,cfg4-R,cfg5,cfg5-wrap}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ARGS="--headline cfg3 --configs $SIDE --extras none --steps 3 --warmup 1 --side-steps 3 --no-cpu-baseline --corpus-cache /tmp/xlz_corpus_cache"
+ARGS="--full --headline cfg3 --configs $SIDE --extras none --steps 3 --warmup 1 --side-steps 3 --no-cpu-baseline --corpus-cache /tmp/xlz_corpus_cache"
 echo "bench args: $ARGS" > $O/command.txt
 run() { # name, rocprofv3 options
     local n=$1; shift
