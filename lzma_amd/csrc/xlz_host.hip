@@ -786,6 +786,107 @@ int batch_free(xlz_batch *b)
     return XLZ_OK;
 }
 
+// Takes the context's pinned input image for one pack + upload, at least `bytes` of it (grow-only: + 25 % + 1 MiB), and
+// makes sure of the stream its uploads go on.
+int take_pin_in(PinLease &lease, HostPipe &hp, size_t bytes)
+{
+    lease.take(hp);
+    if (hp.pin_in_cap < bytes) {
+        if (hp.pin_in) (void)hipHostFree(hp.pin_in);
+        hp.pin_in = nullptr;
+        hp.pin_in_cap = 0;
+        const size_t want = bytes + bytes / 4 + (1u << 20);
+        if (hipHostMalloc(&hp.pin_in, want, hipHostMallocDefault) != hipSuccess) return XLZ_ERR_DEVICE;
+        hp.pin_in_cap = want;
+    }
+    if (!hp.up_stream && hipStreamCreateWithFlags(&hp.up_stream, hipStreamNonBlocking) != hipSuccess) return XLZ_ERR_DEVICE;
+    return XLZ_OK;
+}
+
+struct PackPiece {
+    uint64_t off; // in the pinned image and in the destination
+    const uint8_t *src;
+    size_t len;
+};
+
+// Packs pieces at(0) ... at(n - 1) (ascending offsets inside [0, total)) into `stage`, a range of the pinned input image,
+// and copies them to the same offsets of `dst` on the context's up_stream: host threads each pack a contiguous run of the
+// pieces, and every ~16 MiB one of them has packed goes to the device while the packing goes on.  zero_gaps: the bytes
+// around the pieces are zeroed and copied too, all of [0, total) (an input arena's padding: the decoder's input window may
+// run into it).
+template <class At> int pack_upload(xlz_ctx *ctx, uint8_t *stage, uint8_t *dst, size_t n, uint64_t total, bool zero_gaps, At &&at)
+{
+    const hipStream_t up = ctx->pipe.up_stream;
+    std::atomic<bool> copy_failed{false};
+    auto copy = [&](uint64_t from, uint64_t to) {
+        if (to > from && hipMemcpyAsync(dst + from, stage + from, (size_t)(to - from), hipMemcpyHostToDevice, up) != hipSuccess)
+            copy_failed = true;
+    };
+    if (!n && zero_gaps) {
+        memset(stage, 0, (size_t)total);
+        copy(0, total);
+    }
+    // where the bytes packed with piece k end: the piece's end, or with zero_gaps the next piece's start
+    auto end_of = [&](size_t k) {
+        if (!zero_gaps) return at(k).off + at(k).len;
+        return k + 1 < n ? at(k + 1).off : total;
+    };
+    const unsigned nth = host_threads((size_t)total);
+    run_threads(nth, [&](unsigned t) {
+        (void)hipSetDevice(ctx->device);
+        const size_t k0 = n * t / nth, k1 = n * (t + 1) / nth;
+        if (k0 >= k1) return;
+        uint64_t sent = at(k0).off;
+        if (zero_gaps && k0 == 0) {
+            memset(stage, 0, (size_t)sent);
+            sent = 0;
+        }
+        for (size_t k = k0; k < k1; k++) {
+            const PackPiece pc = at(k);
+            memcpy(stage + pc.off, pc.src, pc.len);
+            const uint64_t end = end_of(k);
+            if (end > pc.off + pc.len) memset(stage + pc.off + pc.len, 0, (size_t)(end - pc.off - pc.len));
+            if (end - sent >= (16u << 20)) {
+                copy(sent, end);
+                sent = end;
+            }
+        }
+        copy(sent, end_of(k1 - 1));
+    });
+    return copy_failed ? XLZ_ERR_DEVICE : XLZ_OK;
+}
+
+// The launch over a batch's LDS-model units (big = false) or over its HBM-model units, as xlz_batch_run queues it: the
+// batch's arenas, unit table, order, results and queue, and the model storage of those units.  A re-run (run_units) and a
+// slice override what they do differently.
+LaunchParams batch_params(const xlz_batch *b, bool big)
+{
+    LaunchParams p;
+    memset(&p, 0, sizeof p); // (epochs, slices, head_frac, ...: off unless a caller sets them)
+    p.in_arena = b->d_in;
+    p.out_arena = b->d_out;
+    p.units = b->d_units;
+    p.order = b->d_order;
+    p.results = b->d_results;
+    p.queue = b->queue ? b->queue : b->ctx->queue;
+    p.prio_tab = b->ctx->prio_tab;
+    p.call_units = b->call_units;
+    if (big) { // models in HBM (lc+lp > 8): the full layout, the model and its matched-literal part in a scratch slot
+        p.n_units = (uint32_t)b->units.size() - b->n_normal;
+        p.order_base = b->n_normal;
+        p.max_lc_lp = b->max_lc_lp_big;
+        p.scratch = b->d_scratch;
+        p.scratch_stride = b->scratch_stride;
+    } else { // models in LDS
+        p.n_units = b->n_normal;
+        p.max_lc_lp = b->max_lc_lp;
+        p.mlit = b->d_mlit;
+        p.mlit_stride = b->mlit_stride;
+        p.compact = b->compact ? 1u : 0u;
+    }
+    return p;
+}
+
 } // namespace
 
 // How xlz_decode_batch wants a (sub-)batch made.  want_slices > 1: a sliced batch (xlz_batch: slice_*) if every unit's model
@@ -1067,48 +1168,20 @@ static int batch_create_ex(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t 
             (!tails->empty() && hipMemcpy(b->d_up_pieces + heads->size(), tails->data(), tails->size() * sizeof(SlicePiece),
                                           hipMemcpyHostToDevice) != hipSuccess))
             return fail(XLZ_ERR_DEVICE);
-        b->in_lease.take(hp);
-        if (hp.pin_in_cap < A + B) {
-            if (hp.pin_in) (void)hipHostFree(hp.pin_in);
-            hp.pin_in = nullptr;
-            hp.pin_in_cap = 0;
-            const size_t want = (size_t)(A + B) + (size_t)(A + B) / 4 + (1u << 20);
-            if (hipHostMalloc(&hp.pin_in, want, hipHostMallocDefault) != hipSuccess) return fail(XLZ_ERR_DEVICE);
-            hp.pin_in_cap = want;
-        }
-        if (!hp.up_stream && hipStreamCreateWithFlags(&hp.up_stream, hipStreamNonBlocking) != hipSuccess) return fail(XLZ_ERR_DEVICE);
-        // one part of the upload: pack its pieces into the pinned image (several host threads, each a contiguous run of the
-        // pieces, ~16 MiB to the device at a time while the packing goes on), then scatter the part into the arena
+        if (take_pin_in(b->in_lease, hp, (size_t)(A + B)) != XLZ_OK) return fail(XLZ_ERR_DEVICE);
+        // one part of the upload: pack its pieces into the pinned image and bring them to the staging range, then scatter
+        // the part into the arena
         auto upload_part = [b, ctx, streams, unit_src_off_p](const std::vector<SlicePiece> &pv, size_t table_at, uint64_t zone,
                                                              uint64_t zone_bytes, hipEvent_t done) -> int {
             HostPipe &hp = ctx->pipe;
-            uint8_t *stage = hp.pin_in + zone;
-            const unsigned nth = host_threads((size_t)zone_bytes);
-            std::atomic<bool> copy_failed{false};
-            const size_t np = pv.size();
-            auto pack = [&](unsigned t) {
-                (void)hipSetDevice(ctx->device);
-                const size_t k0 = np * t / nth, k1 = np * (t + 1) / nth;
-                if (k0 >= k1) return;
-                uint64_t sent = pv[k0].pack_off;
-                auto flush_to = [&](uint64_t end) {
-                    if (end > sent && hipMemcpyAsync(b->d_stage + zone + sent, stage + sent, (size_t)(end - sent), hipMemcpyHostToDevice,
-                                                     hp.up_stream) != hipSuccess)
-                        copy_failed = true;
-                    sent = end;
-                };
-                for (size_t k = k0; k < k1; k++) {
-                    const SlicePiece &pc = pv[k];
-                    const Unit &u = b->units[pc.unit];
-                    memcpy(stage + pc.pack_off, streams[u.stream].in + (*unit_src_off_p)[pc.unit] + (pc.src_off - u.in_off), pc.len);
-                    if (pc.pack_off + pc.len - sent >= (16u << 20)) flush_to(pc.pack_off + pc.len);
-                }
-                flush_to(pv[k1 - 1].pack_off + pv[k1 - 1].len);
-            };
-            run_threads(nth, pack);
-            if (copy_failed) return XLZ_ERR_DEVICE;
-            if (launch_gather(b->d_up_pieces + table_at, (uint32_t)np, b->d_in, b->d_stage + zone, zone_bytes, ctx->num_cus, hp.up_stream,
-                              true) != 0)
+            const int st = pack_upload(ctx, hp.pin_in + zone, b->d_stage + zone, pv.size(), zone_bytes, false, [&](size_t k) {
+                const SlicePiece &pc = pv[k];
+                const Unit &u = b->units[pc.unit];
+                return PackPiece{pc.pack_off, streams[u.stream].in + (*unit_src_off_p)[pc.unit] + (pc.src_off - u.in_off), pc.len};
+            });
+            if (st != XLZ_OK) return st;
+            if (launch_gather(b->d_up_pieces + table_at, (uint32_t)pv.size(), b->d_in, b->d_stage + zone, zone_bytes, ctx->num_cus,
+                              hp.up_stream, true) != 0)
                 return XLZ_ERR_DEVICE;
             return hipEventRecord(done, hp.up_stream) == hipSuccess ? XLZ_OK : XLZ_ERR_DEVICE;
         };
@@ -1119,54 +1192,16 @@ static int batch_create_ex(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t 
         const size_t n_heads = heads->size();
         b->upload_tails = [upload_part, tails, n_heads, A, B, b]() { return upload_part(*tails, n_heads, A, B, b->ev_tails); };
     } else {
-        // pack the payloads into the context's pinned image (several host threads), one H2D copy
+        // the payloads at their arena offsets, the padding zeroed, straight into the input arena (units are laid out in
+        // arena order)
         HostPipe &hp = ctx->pipe;
         PinLease lease;
-        lease.take(hp);
-        if (hp.pin_in_cap < b->in_bytes) {
-            if (hp.pin_in) (void)hipHostFree(hp.pin_in);
-            hp.pin_in = nullptr;
-            hp.pin_in_cap = 0;
-            const size_t want = b->in_bytes + b->in_bytes / 4 + (1u << 20);
-            if (hipHostMalloc(&hp.pin_in, want, hipHostMallocDefault) != hipSuccess) return fail(XLZ_ERR_DEVICE);
-            hp.pin_in_cap = want;
-        }
-        uint8_t *stage = hp.pin_in;
-        if (!hp.up_stream && hipStreamCreateWithFlags(&hp.up_stream, hipStreamNonBlocking) != hipSuccess) return fail(XLZ_ERR_DEVICE);
-        const unsigned nth = host_threads(b->in_bytes);
-        std::atomic<bool> copy_failed{false};
-        auto pack = [&](unsigned t) {
-            // units are laid out in arena order: thread t owns a contiguous run of them and the
-            // padding bytes that follow each (zeroed: the decoder's input window may run into them).
-            // Every ~16 MiB it has packed go to the device at once: the bus works while the packing goes on.
-            (void)hipSetDevice(ctx->device);
-            const size_t k0 = nu * t / nth, k1 = nu * (t + 1) / nth;
-            if (k0 >= k1) return;
-            uint64_t sent = b->units[k0].in_off;
-            if (t == 0) sent = 0;
-            auto flush_to = [&](uint64_t end) {
-                if (end > sent && hipMemcpyAsync(b->d_in + sent, stage + sent, (size_t)(end - sent), hipMemcpyHostToDevice,
-                                                 hp.up_stream) != hipSuccess)
-                    copy_failed = true;
-                sent = end;
-            };
-            for (size_t k = k0; k < k1; k++) {
-                const Unit &u = b->units[k];
-                memcpy(stage + u.in_off, streams[u.stream].in + unit_src_off[k], u.in_len);
-                const uint64_t end = u.in_off + u.in_len;
-                const uint64_t next = k + 1 < nu ? b->units[k + 1].in_off : b->in_bytes;
-                if (next > end) memset(stage + end, 0, (size_t)(next - end));
-                if (next - sent >= (16u << 20)) flush_to(next);
-            }
-            flush_to(k1 < nu ? b->units[k1].in_off : b->in_bytes);
-        };
-        if (nu && b->units[0].in_off) memset(stage, 0, (size_t)b->units[0].in_off);
-        if (!nu) {
-            memset(stage, 0, b->in_bytes);
-            if (hipMemcpyAsync(b->d_in, stage, b->in_bytes, hipMemcpyHostToDevice, hp.up_stream) != hipSuccess) copy_failed = true;
-        }
-        run_threads(nth, pack);
-        if (hipStreamSynchronize(hp.up_stream) != hipSuccess || copy_failed) return fail(XLZ_ERR_DEVICE);
+        if (take_pin_in(lease, hp, b->in_bytes) != XLZ_OK) return fail(XLZ_ERR_DEVICE);
+        const int st = pack_upload(ctx, hp.pin_in, b->d_in, nu, b->in_bytes, true, [&](size_t k) {
+            const Unit &u = b->units[k];
+            return PackPiece{u.in_off, streams[u.stream].in + unit_src_off[k], u.in_len};
+        });
+        if (hipStreamSynchronize(hp.up_stream) != hipSuccess || st != XLZ_OK) return fail(XLZ_ERR_DEVICE);
     }
     if (nu) {
         if (hipMemcpy(b->d_units, b->units.data(), nu * sizeof(Unit), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1188,27 +1223,9 @@ extern "C" int xlz_batch_run(xlz_batch *b)
     uint32_t *const rq = b->queue ? b->queue : ctx->queue;
     HIP_TRY(hipMemsetAsync(rq, 0, 256, rs));
     HIP_TRY(hipEventRecord(b->ev0, rs));
-    const uint32_t nu = (uint32_t)b->units.size();
-    LaunchParams p;
-    memset(&p, 0, sizeof p); // (ready, epochs, ...: off unless set below)
-    p.in_arena = b->d_in;
-    p.out_arena = b->d_out;
-    p.units = b->d_units;
-    p.order = b->d_order;
-    p.results = b->d_results;
-    p.queue = rq;
-    p.prio_tab = ctx->prio_tab;
-    p.call_units = b->call_units;
-    p.epochs = nullptr; // ordinary launch: copies that reach across a dictionary reset are only flagged
+    // (ordinary launches, no epoch tables: copies that reach across a dictionary reset are only flagged)
     if (b->n_normal) { // models in LDS
-        p.n_units = b->n_normal;
-        p.max_lc_lp = b->max_lc_lp;
-        p.compact = b->compact ? 1u : 0u;
-        p.scratch = nullptr;
-        p.scratch_stride = 0;
-        p.mlit = b->d_mlit;
-        p.mlit_stride = b->mlit_stride;
-        p.order_base = 0;
+        LaunchParams p = batch_params(b, false);
         if (b->slice_fracs.empty()) {
             if (launch_decode(p, ctx->num_cus, rs) != 0) return XLZ_ERR_DEVICE;
         } else { // a sequence of launches, each up to the next output bound of every unit (all queued at once)
@@ -1227,9 +1244,6 @@ extern "C" int xlz_batch_run(xlz_batch *b)
                 if (launch_decode(p, ctx->num_cus, rs) != 0) return XLZ_ERR_DEVICE;
                 HIP_TRY(hipEventRecord(b->slice_ev[k], rs));
             }
-            p.slice_frac = 0;
-            p.slice_k = 0;
-            p.head_frac = 0;
             if (b->head_frac) { // the pinned image is free again when the tails have left it
                 HIP_TRY(hipEventSynchronize(b->ev_tails));
                 b->in_lease.release();
@@ -1237,17 +1251,9 @@ extern "C" int xlz_batch_run(xlz_batch *b)
             }
         }
     }
-    if (nu > b->n_normal) { // models in HBM (lc+lp > 8): the full layout
-        p.compact = 0;
+    if (b->units.size() > b->n_normal) { // models in HBM
         HIP_TRY(hipMemsetAsync(rq, 0, 256, rs));
-        p.n_units = nu - b->n_normal;
-        p.max_lc_lp = b->max_lc_lp_big;
-        p.scratch = b->d_scratch;
-        p.scratch_stride = b->scratch_stride;
-        p.mlit = nullptr;
-        p.mlit_stride = 0;
-        p.order_base = b->n_normal;
-        if (launch_decode(p, ctx->num_cus, rs) != 0) return XLZ_ERR_DEVICE;
+        if (launch_decode(batch_params(b, true), ctx->num_cus, rs) != 0) return XLZ_ERR_DEVICE;
     }
     HIP_TRY(hipEventRecord(b->ev1, rs));
     b->ran = true;
@@ -1277,7 +1283,8 @@ namespace {
 // Launch `units` (already laid out against the batch's arenas) and fetch their results.  These are
 // always EXACT launches: every workgroup gets an epoch table, so copies that reach across an LZMA2
 // dictionary reset read the bytes the reference's uncleared window holds (window.go:135-140).
-// wide_lc_lp != 0: an HBM-model launch of its own with room for models up to that lc + lp (scratch allocated here)
+// wide_lc_lp != 0 (big units only): an HBM-model launch of its own with room for models up to that lc + lp (scratch
+// allocated here)
 int run_units(xlz_batch *b, const std::vector<Unit> &units, std::vector<UnitResult> &res, bool big, uint32_t wide_lc_lp = 0)
 {
     xlz_ctx *ctx = b->ctx;
@@ -1306,24 +1313,20 @@ int run_units(xlz_batch *b, const std::vector<Unit> &units, std::vector<UnitResu
         hipMemcpy(d_units, units.data(), n * sizeof(Unit), hipMemcpyHostToDevice) == hipSuccess &&
         hipMemcpy(d_order, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
         hipMemsetAsync(ctx->queue, 0, 256, ctx->stream) == hipSuccess) {
-        LaunchParams p;
-        memset(&p, 0, sizeof p); // (epochs, order_base, ...: off unless set below)
-        p.in_arena = b->d_in;
-        p.out_arena = b->d_out;
+        LaunchParams p = batch_params(b, big);
         p.units = d_units;
         p.order = d_order;
         p.results = d_res;
-        p.queue = ctx->queue;
+        p.queue = ctx->queue; // (on the context's stream, whichever stream the batch's own launches went to)
         p.n_units = (uint32_t)n;
-        p.max_lc_lp = wide_lc_lp ? wide_lc_lp : big ? b->max_lc_lp_big : b->max_lc_lp;
-        p.scratch = wide_lc_lp ? d_wide : big ? b->d_scratch : nullptr;
-        p.scratch_stride = wide_lc_lp ? wide_stride : big ? b->scratch_stride : 0;
-        p.mlit = big ? nullptr : b->d_mlit;
-        p.mlit_stride = big ? 0 : b->mlit_stride;
-        p.compact = (!big && !wide_lc_lp && b->compact) ? 1u : 0u;
         p.order_base = 0;
+        p.call_units = 0; // (the grid follows these units alone)
         p.epochs = d_epochs;
-        p.prio_tab = ctx->prio_tab;
+        if (wide_lc_lp) {
+            p.max_lc_lp = wide_lc_lp;
+            p.scratch = d_wide;
+            p.scratch_stride = wide_stride;
+        }
         if (launch_decode(p, ctx->num_cus, ctx->stream, wide_lc_lp ? grid : 0) == 0 && hipStreamSynchronize(ctx->stream) == hipSuccess &&
             hipMemcpy(res.data(), d_res, n * sizeof(UnitResult), hipMemcpyDeviceToHost) == hipSuccess)
             st = XLZ_OK;
@@ -1336,36 +1339,11 @@ int run_units(xlz_batch *b, const std::vector<Unit> &units, std::vector<UnitResu
     return st;
 }
 
-void fold_streams(xlz_batch *b, size_t s0, size_t s1, std::vector<size_t> &redo);
-int finish_collect(xlz_batch *b, const std::vector<size_t> &redo);
-
-// Sync, fetch unit results, fold them into per-stream results.  An LZMA2 stream whose
-// units did not produce / consume exactly what its chunk headers announced is decoded
-// again as ONE unit: that pass follows the reference's framing byte for byte.
-int collect(xlz_batch *b)
-{
-    if (b->collected) return XLZ_OK;
-    xlz_ctx *ctx = b->ctx;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventSynchronize(b->ev1)); // this batch's launches (a later batch may already be queued behind them)
-    std::vector<UnitResult> &ur = b->unit_results;
-    ur.resize(b->units.size());
-    if (!ur.empty())
-        HIP_TRY(hipMemcpy(ur.data(), b->d_results, ur.size() * sizeof(UnitResult), hipMemcpyDeviceToHost));
-    b->final_results.assign(b->n, xlz_result{});
-    b->rewritten.clear();
-    b->wants_wide.assign(b->n, 0);
-    std::vector<size_t> redo;
-    fold_streams(b, 0, b->n, redo);
-    return finish_collect(b, redo);
-}
-
-// unit results -> per-stream results for streams [s0, s1); streams that need the exact re-run go to `redo`
-void fold_streams(xlz_batch *b, size_t s0, size_t s1, std::vector<size_t> &redo)
+// unit results -> per-stream results; streams that need the exact re-run go to `redo`
+void fold_streams(xlz_batch *b, std::vector<size_t> &redo)
 {
     const std::vector<UnitResult> &ur = b->unit_results;
-    for (size_t i = s0; i < s1; i++) {
+    for (size_t i = 0; i < b->n; i++) {
         const StreamPlan &pl = b->plans[i];
         xlz_result &r = b->final_results[i];
         if (pl.host_status != 1) { // settled while parsing
@@ -1429,43 +1407,72 @@ void fold_streams(xlz_batch *b, size_t s0, size_t s1, std::vector<size_t> &redo)
     }
 }
 
-// the exact single-unit re-run of the streams in `redo` (malformed LZMA2 only), then the byte sums
-int finish_collect(xlz_batch *b, const std::vector<size_t> &redo)
+// stream i (LZMA2) as ONE unit of a re-run, with room for models up to lc + lp = lc_lp
+Unit whole_stream_unit(const xlz_batch *b, size_t i, uint32_t lc_lp, bool big)
 {
+    const StreamPlan &pl = b->plans[i];
+    Unit u;
+    memset(&u, 0, sizeof u);
+    u.kind = UNIT_LZMA2;
+    u.in_off = pl.in_off;
+    u.in_len = pl.in_len;
+    u.out_off = pl.out_off;
+    u.out_cap = (uint32_t)pl.out_cap;
+    u.dict_size = pl.dict_size;
+    u.unpack_size = kUnknownSize;
+    u.stream = (uint32_t)i;
+    u.lc = (uint8_t)lc_lp;
+    u.flags = UNIT_F_LAST | (big ? UNIT_F_BIG_MODEL : 0u);
+    return u;
+}
+
+// Decodes the streams `idx` again, each as ONE unit of an exact launch (run_units: big, wide_lc_lp), and puts what they
+// made in place of their results; their bytes were written again (xlz_batch::rewritten).
+int rerun_streams(xlz_batch *b, const std::vector<size_t> &idx, bool big, uint32_t wide_lc_lp = 0)
+{
+    std::vector<Unit> units;
+    for (size_t i : idx) units.push_back(whole_stream_unit(b, i, wide_lc_lp ? wide_lc_lp : b->units[b->plans[i].first_unit].lc, big));
+    std::vector<UnitResult> res;
+    const int st = run_units(b, units, res, big, wide_lc_lp);
+    if (st != XLZ_OK) return st;
+    for (size_t k = 0; k < idx.size(); k++) {
+        xlz_result &r = b->final_results[idx[k]];
+        r.status = res[k].status;
+        r.out_len = res[k].out_len;
+        r.in_consumed = res[k].in_consumed;
+        b->rewritten.push_back(idx[k]);
+        b->wants_wide[idx[k]] = (res[k].status == ST_ERR_UNSUPPORTED && (res[k].aux & AUX_GROW)) ? 1 : 0;
+    }
+    return XLZ_OK;
+}
+
+// Sync, fetch unit results, fold them into per-stream results.  An LZMA2 stream whose
+// units did not produce / consume exactly what its chunk headers announced is decoded
+// again as ONE unit: that pass follows the reference's framing byte for byte.
+int collect(xlz_batch *b)
+{
+    if (b->collected) return XLZ_OK;
+    xlz_ctx *ctx = b->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventSynchronize(b->ev1)); // this batch's launches (a later batch may already be queued behind them)
+    std::vector<UnitResult> &ur = b->unit_results;
+    ur.resize(b->units.size());
+    if (!ur.empty())
+        HIP_TRY(hipMemcpy(ur.data(), b->d_results, ur.size() * sizeof(UnitResult), hipMemcpyDeviceToHost));
+    b->final_results.assign(b->n, xlz_result{});
+    b->rewritten.clear();
+    b->wants_wide.assign(b->n, 0);
+    std::vector<size_t> redo;
+    fold_streams(b, redo);
+    // the exact re-run of the streams in `redo` (malformed LZMA2 only): those of LDS-model units, then those of HBM-model ones
     for (int pass = 0; pass < 2 && !redo.empty(); pass++) {
         const bool big = pass == 1;
-        std::vector<Unit> units;
         std::vector<size_t> idx;
-        for (size_t i : redo) {
-            if (((b->units[b->plans[i].first_unit].flags & UNIT_F_BIG_MODEL) != 0) != big) continue;
-            idx.push_back(i);
-            const StreamPlan &pl = b->plans[i];
-            Unit u;
-            memset(&u, 0, sizeof u);
-            u.kind = UNIT_LZMA2;
-            u.in_off = pl.in_off;
-            u.in_len = pl.in_len;
-            u.out_off = pl.out_off;
-            u.out_cap = (uint32_t)pl.out_cap;
-            u.dict_size = pl.dict_size;
-            u.unpack_size = kUnknownSize;
-            u.stream = (uint32_t)i;
-            u.lc = b->units[pl.first_unit].lc;
-            u.flags = UNIT_F_LAST | (big ? UNIT_F_BIG_MODEL : 0u);
-            units.push_back(u);
-        }
-        if (units.empty()) continue;
-        std::vector<UnitResult> res;
-        int st = run_units(b, units, res, big);
+        for (size_t i : redo)
+            if (((b->units[b->plans[i].first_unit].flags & UNIT_F_BIG_MODEL) != 0) == big) idx.push_back(i);
+        const int st = rerun_streams(b, idx, big);
         if (st != XLZ_OK) return st;
-        for (size_t k = 0; k < idx.size(); k++) {
-            xlz_result &r = b->final_results[idx[k]];
-            r.status = res[k].status;
-            r.out_len = res[k].out_len;
-            r.in_consumed = res[k].in_consumed;
-            b->rewritten.push_back(idx[k]);
-            b->wants_wide[idx[k]] = (res[k].status == ST_ERR_UNSUPPORTED && (res[k].aux & AUX_GROW)) ? 1 : 0;
-        }
     }
     // The model's storage (LDS, or a workgroup's HBM slot) is sized by the host's scan of the chunk HEADERS.  A malformed stream
     // whose real decode leaves its headers can walk into bytes that read as a chunk with larger properties than any the scan
@@ -1474,44 +1481,17 @@ int finish_collect(xlz_batch *b, const std::vector<size_t> &redo)
     // launch with room for the largest model the reference accepts (found by tools/fuzz_gpu.py in round 4, seed 5501:
     // tests/golden/fuzz_5501_18774.lzma2; sessions have had AUX_GROW for this since round 3, slices of a stream leave it
     // to their caller).
-    {
-        std::vector<Unit> units;
-        std::vector<size_t> idx;
-        for (size_t i = 0; i < b->n; i++) {
-            const StreamPlan &pl = b->plans[i];
-            // (only streams that stopped in front of LARGER PROPERTIES: a re-run cannot help a full epoch table -- ADVICE r4)
-            if (pl.host_status != 1 || !pl.lzma2 || pl.slice || b->final_results[i].status != XLZ_ERR_UNSUPPORTED || !b->wants_wide[i]) continue;
-            idx.push_back(i);
-            Unit u;
-            memset(&u, 0, sizeof u);
-            u.kind = UNIT_LZMA2;
-            u.in_off = pl.in_off;
-            u.in_len = pl.in_len;
-            u.out_off = pl.out_off;
-            u.out_cap = (uint32_t)pl.out_cap;
-            u.dict_size = pl.dict_size;
-            u.unpack_size = kUnknownSize;
-            u.stream = (uint32_t)i;
-            u.lc = (uint8_t)kMaxLcLp;
-            u.flags = UNIT_F_LAST | UNIT_F_BIG_MODEL;
-            units.push_back(u);
-        }
-        if (!units.empty()) {
-            std::vector<UnitResult> res;
-            int st = run_units(b, units, res, true, kMaxLcLp);
-            // no memory for the widest models (6 MiB per workgroup): these streams stay at XLZ_ERR_UNSUPPORTED, the call and
-            // the other streams' results stand -- one crafted stream must not fail a batch
-            if (st == XLZ_ERR_NO_MEMORY_INTERNAL) idx.clear();
-            else if (st != XLZ_OK) return st;
-            for (size_t k = 0; k < idx.size(); k++) {
-                xlz_result &r = b->final_results[idx[k]];
-                r.status = res[k].status;
-                r.out_len = res[k].out_len;
-                r.in_consumed = res[k].in_consumed;
-                b->rewritten.push_back(idx[k]);
-            }
-        }
+    std::vector<size_t> wide;
+    for (size_t i = 0; i < b->n; i++) {
+        const StreamPlan &pl = b->plans[i];
+        // (only streams that stopped in front of LARGER PROPERTIES: a re-run cannot help a full epoch table -- ADVICE r4)
+        if (pl.host_status == 1 && pl.lzma2 && !pl.slice && b->final_results[i].status == XLZ_ERR_UNSUPPORTED && b->wants_wide[i])
+            wide.push_back(i);
     }
+    // no memory for the widest models (6 MiB per workgroup): these streams stay at XLZ_ERR_UNSUPPORTED, the call and the
+    // other streams' results stand -- one crafted stream must not fail a batch
+    const int st = rerun_streams(b, wide, true, kMaxLcLp);
+    if (st != XLZ_OK && st != XLZ_ERR_NO_MEMORY_INTERNAL) return st;
     std::sort(b->rewritten.begin(), b->rewritten.end());
     b->rewritten.erase(std::unique(b->rewritten.begin(), b->rewritten.end()), b->rewritten.end());
     b->sum_in = b->sum_out = 0;
@@ -1611,14 +1591,102 @@ extern "C" void xlz_batch_destroy(xlz_batch *b) { batch_free(b); }
 
 namespace {
 
+// Moves n chunks from the device to the callers' buffers through the context's pinned ring (one download at a time per
+// context).  On this thread, for j = 0 ... n: before(j, copy_stream) queues what chunk j needs on the copy stream (false:
+// failed; before(n) runs behind the last chunk), then chunk j, src(j) = {device bytes, length} of at most
+// HostPipe::kRingBytes, is copied into slot j % kRing, which it takes over once the slot's previous chunk has been
+// scattered.  Host threads claim the chunks in order and, when one has arrived, scatter(j, slot bytes) it.
+struct RingChunk {
+    const uint8_t *src;
+    size_t len;
+};
+template <class Before, class Src, class Scatter>
+int ring_download(xlz_batch *b, size_t n, Before &&before, Src &&src, Scatter &&scatter)
+{
+    xlz_ctx *ctx = b->ctx;
+    HostPipe &hp = ctx->pipe;
+    std::lock_guard<std::mutex> out_lock(hp.mu_out);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!hp.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&hp.copy_stream, hipStreamNonBlocking));
+    for (int r = 0; r < HostPipe::kRing; r++) {
+        if (!hp.ring[r]) HIP_TRY(hipHostMalloc(&hp.ring[r], HostPipe::kRingBytes, hipHostMallocDefault));
+        if (!hp.ring_ev[r]) HIP_TRY(hipEventCreateWithFlags(&hp.ring_ev[r], hipEventDisableTiming));
+    }
+    // scatter workers: chunk j is claimed by one worker, which waits for its copy event
+    const unsigned nworkers = std::min<unsigned>(host_threads(b->out_bytes), HostPipe::kRing);
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t issued = 0, next_claim = 0, n_done = 0; // chunks whose D2H was issued / claimed / scattered
+    std::vector<char> done(n, 0);
+    bool failed = false;
+    auto worker = [&] {
+        (void)hipSetDevice(ctx->device);
+        for (;;) {
+            size_t j;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return next_claim < issued || next_claim >= n || failed; });
+                if (failed || next_claim >= n) return;
+                j = next_claim++;
+            }
+            const int slot = (int)(j % HostPipe::kRing);
+            const bool ok = hipEventSynchronize(hp.ring_ev[slot]) == hipSuccess;
+            if (ok) scatter(j, hp.ring[slot]);
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                done[j] = 1;
+                n_done++;
+                if (!ok) failed = true;
+            }
+            cv.notify_all();
+        }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nworkers; t++) th.emplace_back(worker);
+    int st = XLZ_OK;
+    for (size_t j = 0; j <= n; j++) {
+        if (!before(j, hp.copy_stream)) {
+            st = XLZ_ERR_DEVICE;
+            break;
+        }
+        if (j == n) break;
+        const int slot = (int)(j % HostPipe::kRing);
+        if (j >= (size_t)HostPipe::kRing) { // the slot's previous chunk must have been scattered
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return done[j - HostPipe::kRing] || failed; });
+            if (failed) break;
+        }
+        const RingChunk c = src(j);
+        if (hipMemcpyAsync(hp.ring[slot], c.src, c.len, hipMemcpyDeviceToHost, hp.copy_stream) != hipSuccess ||
+            hipEventRecord(hp.ring_ev[slot], hp.copy_stream) != hipSuccess) {
+            st = XLZ_ERR_DEVICE;
+            break;
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            issued = j + 1;
+        }
+        cv.notify_all();
+    }
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        if (st != XLZ_OK) failed = true;
+        if (!failed) cv.wait(lk, [&] { return n_done == n || failed; });
+        if (failed) st = XLZ_ERR_DEVICE;
+        next_claim = std::max(next_claim, n); // release idle workers
+    }
+    cv.notify_all();
+    for (auto &x : th) x.join();
+    if (hipStreamSynchronize(hp.copy_stream) != hipSuccess) st = XLZ_ERR_DEVICE;
+    return st;
+}
+
 // All decoded streams of a batch to the callers' buffers: the output arena is cut into chunks of
 // at most HostPipe::kRingBytes (whole stream regions where they fit, pieces of a region where one
 // does not), each chunk is copied D2H into a slot of the pinned ring on the copy stream, and host
 // threads scatter the chunks that have arrived while the next ones are in flight.
 int download_all(xlz_batch *b, const xlz_stream_desc *streams, const xlz_result *results, const std::vector<size_t> *only = nullptr)
 {
-    xlz_ctx *ctx = b->ctx;
-    HostPipe &hp = ctx->pipe;
     struct Piece {
         uint64_t dev_off;
         uint8_t *dst;
@@ -1655,89 +1723,38 @@ int download_all(xlz_batch *b, const xlz_stream_desc *streams, const xlz_result 
         }
     }
     if (chunks.empty()) return XLZ_OK;
-
-    std::lock_guard<std::mutex> pl(hp.mu_out);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!hp.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&hp.copy_stream, hipStreamNonBlocking));
-    for (int r = 0; r < HostPipe::kRing; r++) {
-        if (!hp.ring[r]) HIP_TRY(hipHostMalloc(&hp.ring[r], HostPipe::kRingBytes, hipHostMallocDefault));
-        if (!hp.ring_ev[r]) HIP_TRY(hipEventCreateWithFlags(&hp.ring_ev[r], hipEventDisableTiming));
-    }
-    // the decode of THIS batch has finished (its results were read).  Not hipStreamSynchronize(ctx->stream): in a
-    // pipelined call the next sub-batch is decoding on that stream right now, and waiting for it is what made round 2's
-    // overlap experiments look as if "a copy does not start under a running launch" (it does: tools/overlap_probe.py)
-    HIP_TRY(hipEventSynchronize(b->ev1));
-
-    // scatter workers: chunk k is claimed by one worker, which waits for its copy event
-    const unsigned nworkers = std::min<unsigned>(host_threads(b->out_bytes), HostPipe::kRing);
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t issued = 0, next_claim = 0, n_done = 0; // chunks whose D2H was issued / claimed / scattered
-    std::vector<char> done(chunks.size(), 0);
-    bool failed = false;
-    auto worker = [&] {
-        (void)hipSetDevice(ctx->device);
-        for (;;) {
-            size_t k;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return next_claim < issued || next_claim >= chunks.size() || failed; });
-                if (failed || next_claim >= chunks.size()) return;
-                k = next_claim++;
-            }
-            const int slot = (int)(k % HostPipe::kRing);
-            const bool ok = hipEventSynchronize(hp.ring_ev[slot]) == hipSuccess;
-            if (ok)
-                for (const Piece &pc : chunks[k].pieces)
-                    memcpy(pc.dst, hp.ring[slot] + (pc.dev_off - chunks[k].dev_off), pc.len);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                done[k] = 1;
-                n_done++;
-                if (!ok) failed = true;
-            }
-            cv.notify_all();
-        }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nworkers; t++) th.emplace_back(worker);
-    int st = XLZ_OK;
-    for (size_t k = 0; k < chunks.size(); k++) {
-        const int slot = (int)(k % HostPipe::kRing);
-        if (k >= (size_t)HostPipe::kRing) { // the slot's previous chunk must have been scattered
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return done[k - HostPipe::kRing] || failed; });
-            if (failed) break;
-        }
-        if (hipMemcpyAsync(hp.ring[slot], b->d_out + chunks[k].dev_off, chunks[k].len, hipMemcpyDeviceToHost,
-                           hp.copy_stream) != hipSuccess ||
-            hipEventRecord(hp.ring_ev[slot], hp.copy_stream) != hipSuccess) {
-            std::lock_guard<std::mutex> lk(mu);
-            failed = true;
-            break;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            issued = k + 1;
-        }
-        cv.notify_all();
-    }
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        if (failed) {
-            st = XLZ_ERR_DEVICE;
-        } else {
-            cv.wait(lk, [&] { return n_done == chunks.size() || failed; });
-            if (failed) st = XLZ_ERR_DEVICE;
-        }
-        next_claim = std::max(next_claim, chunks.size()); // release idle workers
-        if (st != XLZ_OK) failed = true;
-    }
-    cv.notify_all();
-    for (auto &x : th) x.join();
-    (void)hipStreamSynchronize(hp.copy_stream);
-    return st;
+    return ring_download(
+        b, chunks.size(),
+        // the decode of THIS batch has finished (its results were read).  Not hipStreamSynchronize(ctx->stream): in a
+        // pipelined call the next sub-batch is decoding on that stream right now, and waiting for it is what made round 2's
+        // overlap experiments look as if "a copy does not start under a running launch" (it does: tools/overlap_probe.py)
+        [&](size_t j, hipStream_t) { return j > 0 || hipEventSynchronize(b->ev1) == hipSuccess; },
+        [&](size_t j) { return RingChunk{b->d_out + chunks[j].dev_off, chunks[j].len}; },
+        [&](size_t j, const uint8_t *ring) {
+            for (const Piece &pc : chunks[j].pieces) memcpy(pc.dst, ring + (pc.dev_off - chunks[j].dev_off), pc.len);
+        });
 }
+
+// Wave-slot bookkeeping of a call from the units' s_memrealtime stamps (100 MHz, the same clock for every launch of the
+// device): busy wave time, first start and last end over ALL sub-batches of the call -- their launches overlap on two
+// streams, so a sub-batch's own span says little; the call's occupancy = busy / (wave slots x (last end - first start)).
+// (download_sliced: the same over the units that ran in one launch of a sliced batch.)
+struct SlotClock {
+    bool any = false;
+    uint32_t ref = 0;        // the first stamp seen: everything else relative to it (the 32-bit clock wraps every 43 s)
+    int64_t first = 0, last = 0;
+    uint64_t busy = 0;
+    void add(const UnitResult &u)
+    {
+        if (!any) ref = u.t_start, first = 0, last = 0, any = true;
+        const int64_t a = (int32_t)(u.t_start - ref), e = (int32_t)(u.t_end - ref);
+        first = std::min(first, a);
+        last = std::max(last, e);
+        busy += (uint32_t)(u.t_end - u.t_start);
+    }
+    double span_ms() const { return any ? (double)(last - first) / 1e5 : 0.0; }
+    double occupancy(uint32_t slots) const { return any && slots && last > first ? (double)busy / ((double)slots * (double)(last - first)) : 0.0; }
+};
 
 // The download of a SLICED batch (xlz_batch: slice_*), running while the launches decode.  Behind launch k (slice_ev[k])
 // the copy stream fetches the unit results, packs the pieces the launch finished into one image (xlz_gather_kernel, next
@@ -1751,7 +1768,6 @@ int download_all(xlz_batch *b, const xlz_stream_desc *streams, const xlz_result 
 int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<double> *per_slice, std::vector<size_t> &gaps)
 {
     xlz_ctx *ctx = b->ctx;
-    HostPipe &hp = ctx->pipe;
     const size_t K = b->slice_fracs.size(), nu = b->units.size();
     struct Chunk {
         uint32_t k;
@@ -1763,14 +1779,23 @@ int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<do
         for (uint64_t off = 0; off < b->slice_pack_bytes[k]; off += HostPipe::kRingBytes)
             chunks.push_back({(uint32_t)k, off, (size_t)std::min<uint64_t>(HostPipe::kRingBytes, b->slice_pack_bytes[k] - off)});
 
-    std::lock_guard<std::mutex> pl(hp.mu_out);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!hp.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&hp.copy_stream, hipStreamNonBlocking));
-    for (int r = 0; r < HostPipe::kRing; r++) {
-        if (!hp.ring[r]) HIP_TRY(hipHostMalloc(&hp.ring[r], HostPipe::kRingBytes, hipHostMallocDefault));
-        if (!hp.ring_ev[r]) HIP_TRY(hipEventCreateWithFlags(&hp.ring_ev[r], hipEventDisableTiming));
-    }
-    auto scatter = [&](const Chunk &c, const uint8_t *ring) {
+    // in front of chunk j: every launch up to the one the chunk is of (behind the last chunk: all of them -- launches that
+    // finish no byte still deliver their results) hands its unit results and its packed pieces to the copy stream
+    size_t next_k = 0, piece_base = 0;
+    auto before = [&](size_t j, hipStream_t cs) {
+        for (const size_t upto = j < chunks.size() ? chunks[j].k : K - 1; next_k <= upto; next_k++) {
+            const size_t k = next_k;
+            if (hipStreamWaitEvent(cs, b->slice_ev[k], 0) != hipSuccess ||
+                hipMemcpyAsync(b->pin_res + k * nu, b->d_results, nu * sizeof(UnitResult), hipMemcpyDeviceToHost, cs) != hipSuccess ||
+                launch_gather(b->d_pieces + piece_base, (uint32_t)b->slice_pieces[k].size(), b->d_out, b->d_pack,
+                              b->slice_pack_bytes[k], ctx->num_cus, cs) != 0)
+                return false;
+            piece_base += b->slice_pieces[k].size();
+        }
+        return true;
+    };
+    auto scatter = [&](size_t j, const uint8_t *ring) {
+        const Chunk &c = chunks[j];
         const std::vector<SlicePiece> &pv = b->slice_pieces[c.k];
         const UnitResult *res = b->pin_res + (size_t)c.k * nu;
         size_t lo = 0, hi = pv.size(); // the piece the chunk starts in
@@ -1793,82 +1818,8 @@ int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<do
             memcpy(dst, ring + (a - c.off), (size_t)(e - a));
         }
     };
-    const unsigned nworkers = std::min<unsigned>(host_threads(b->out_bytes), HostPipe::kRing);
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t issued = 0, next_claim = 0, n_done = 0;
-    std::vector<char> done(chunks.size(), 0);
-    bool failed = false;
-    auto worker = [&] {
-        (void)hipSetDevice(ctx->device);
-        for (;;) {
-            size_t j;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return next_claim < issued || next_claim >= chunks.size() || failed; });
-                if (failed || next_claim >= chunks.size()) return;
-                j = next_claim++;
-            }
-            const int slot = (int)(j % HostPipe::kRing);
-            const bool ok = hipEventSynchronize(hp.ring_ev[slot]) == hipSuccess;
-            if (ok) scatter(chunks[j], hp.ring[slot]);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                done[j] = 1;
-                n_done++;
-                if (!ok) failed = true;
-            }
-            cv.notify_all();
-        }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nworkers; t++) th.emplace_back(worker);
-    int st = XLZ_OK;
-    size_t piece_base = 0;
-    uint32_t slice_begun = ~0u;
-    for (size_t j = 0; j <= chunks.size() && st == XLZ_OK; j++) {
-        // the launches behind the last chunk's one (and launches that finish no byte at all) still deliver their results
-        const uint32_t upto = j < chunks.size() ? chunks[j].k : (uint32_t)(K - 1);
-        while (slice_begun == ~0u || slice_begun < upto) {
-            const uint32_t k = slice_begun + 1;
-            if (hipStreamWaitEvent(hp.copy_stream, b->slice_ev[k], 0) != hipSuccess ||
-                hipMemcpyAsync(b->pin_res + (size_t)k * nu, b->d_results, nu * sizeof(UnitResult), hipMemcpyDeviceToHost,
-                               hp.copy_stream) != hipSuccess ||
-                launch_gather(b->d_pieces + piece_base, (uint32_t)b->slice_pieces[k].size(), b->d_out, b->d_pack,
-                              b->slice_pack_bytes[k], ctx->num_cus, hp.copy_stream) != 0)
-                st = XLZ_ERR_DEVICE;
-            piece_base += b->slice_pieces[k].size();
-            slice_begun = k;
-            if (st != XLZ_OK) break;
-        }
-        if (j == chunks.size() || st != XLZ_OK) break;
-        const int slot = (int)(j % HostPipe::kRing);
-        if (j >= (size_t)HostPipe::kRing) { // the slot's previous chunk must have been scattered
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return done[j - HostPipe::kRing] || failed; });
-            if (failed) break;
-        }
-        if (hipMemcpyAsync(hp.ring[slot], b->d_pack + chunks[j].off, chunks[j].len, hipMemcpyDeviceToHost, hp.copy_stream) != hipSuccess ||
-            hipEventRecord(hp.ring_ev[slot], hp.copy_stream) != hipSuccess) {
-            st = XLZ_ERR_DEVICE;
-            break;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            issued = j + 1;
-        }
-        cv.notify_all();
-    }
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        if (st != XLZ_OK) failed = true;
-        if (!failed) cv.wait(lk, [&] { return n_done == chunks.size() || failed; });
-        if (failed) st = XLZ_ERR_DEVICE;
-        next_claim = std::max(next_claim, chunks.size()); // release idle workers
-    }
-    cv.notify_all();
-    for (auto &x : th) x.join();
-    if (hipStreamSynchronize(hp.copy_stream) != hipSuccess) st = XLZ_ERR_DEVICE;
+    int st = ring_download(
+        b, chunks.size(), before, [&](size_t j) { return RingChunk{b->d_pack + chunks[j].off, chunks[j].len}; }, scatter);
     gaps.clear();
     for (size_t ui = 0; ui < nu && st == XLZ_OK && K > 1; ui++) {
         const Unit &u = b->units[ui];
@@ -1885,28 +1836,18 @@ int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<do
             }
         }
     }
-    if (st == XLZ_OK && per_slice) { // slot occupancy of every launch, from the stamps of the units it ran
-        per_slice->assign(K, 0.0);
+    if (st == XLZ_OK && per_slice) { // slot occupancy of every launch, from the stamps of the units that ran in it
         uint32_t slots = 0;
         (void)xlz_batch_launch_info(b, &slots, nullptr);
-        for (size_t k = 0; k < K && slots; k++) {
+        per_slice->assign(K, 0.0);
+        for (size_t k = 0; k < K; k++) {
             const UnitResult *res = b->pin_res + k * nu, *prev = k ? res - nu : nullptr;
-            uint32_t t0 = 0, span = 0;
-            uint64_t busy = 0;
-            bool any = false;
-            for (size_t ui = 0; ui < nu; ui++) {
-                if (b->units[ui].flags & UNIT_F_BIG_MODEL) continue; // (no result yet)
-                if (prev && prev[ui].t_end == res[ui].t_end && prev[ui].t_start == res[ui].t_start) continue; // did not run
-                if (!any || (int32_t)(res[ui].t_start - t0) < 0) t0 = res[ui].t_start;
-                any = true;
-            }
-            for (size_t ui = 0; ui < nu && any; ui++) {
-                if (b->units[ui].flags & UNIT_F_BIG_MODEL) continue;
-                if (prev && prev[ui].t_end == res[ui].t_end && prev[ui].t_start == res[ui].t_start) continue;
-                busy += (uint32_t)(res[ui].t_end - res[ui].t_start);
-                span = std::max(span, (uint32_t)(res[ui].t_end - t0));
-            }
-            if (span) (*per_slice)[k] = (double)busy / ((double)slots * span);
+            SlotClock launch;
+            for (size_t ui = 0; ui < nu; ui++)
+                if (!(b->units[ui].flags & UNIT_F_BIG_MODEL) && // (no result yet)
+                    !(prev && prev[ui].t_start == res[ui].t_start && prev[ui].t_end == res[ui].t_end)) // (did not run in launch k)
+                    launch.add(res[ui]);
+            (*per_slice)[k] = launch.occupancy(slots);
         }
     }
     return st;
@@ -1915,28 +1856,6 @@ int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<do
 } // namespace
 
 static int decode_oversize(xlz_ctx *ctx, const xlz_stream_desc *streams, xlz_result *results, const std::vector<size_t> &idx);
-
-// Wave-slot bookkeeping of a call from the units' s_memrealtime stamps (100 MHz, the same clock for every launch of the
-// device): busy wave time, first start and last end over ALL sub-batches of the call -- their launches overlap on two
-// streams, so a sub-batch's own span says little; the call's occupancy = busy / (wave slots x (last end - first start)).
-struct SlotClock {
-    bool any = false;
-    uint32_t ref = 0;        // the first stamp seen: everything else relative to it (the 32-bit clock wraps every 43 s)
-    int64_t first = 0, last = 0;
-    uint64_t busy = 0;
-    void add(const std::vector<UnitResult> &ur)
-    {
-        for (const UnitResult &u : ur) {
-            if (!any) ref = u.t_start, first = 0, last = 0, any = true;
-            const int64_t a = (int32_t)(u.t_start - ref), e = (int32_t)(u.t_end - ref);
-            first = std::min(first, a);
-            last = std::max(last, e);
-            busy += (uint32_t)(u.t_end - u.t_start);
-        }
-    }
-    double span_ms() const { return any ? (double)(last - first) / 1e5 : 0.0; }
-    double occupancy(uint32_t slots) const { return any && slots && last > first ? (double)busy / ((double)slots * (double)(last - first)) : 0.0; }
-};
 
 extern "C" int xlz_ctx_set_slicing(xlz_ctx *ctx, uint64_t min_call_bytes, uint64_t slice_bytes, uint32_t max_slices)
 {
@@ -2113,7 +2032,8 @@ extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, si
             (void)xlz_batch_launch_info(sub[k], &slots, nullptr);
             cs.units += sub[k]->unit_results.size();
             cs.wave_slots = std::max(cs.wave_slots, slots);
-            if (sub[k]->slice_fracs.empty()) clock.add(sub[k]->unit_results); // (a sliced call: the mean over its launches, from download_sliced)
+            if (sub[k]->slice_fracs.empty()) // (a sliced call: the mean over its launches, from download_sliced)
+                for (const UnitResult &u : sub[k]->unit_results) clock.add(u);
         }
         if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu decoded at %.1f ms\n", k, now_ms());
         {
