@@ -215,7 +215,9 @@ typedef struct xlz_call_stats {
                               reader1.go:223-254); for a call of one piece decode_ms = the launches (HIP
                               events), download_ms = what was left after them; slot_occupancy = the mean over
                               the launches                                                                */
-    uint32_t reserved;
+    uint32_t refetched;    /* streams of a sliced call downloaded once more after their slices had gone out: a unit
+                              fell short of a launch's bound, a re-run wrote bytes again, or a model beyond LDS
+                              decoded behind the slices (summed over the sub-batches)                       */
 } xlz_call_stats;
 int xlz_ctx_last_call_stats(xlz_ctx *ctx, xlz_call_stats *out);
 /* xlz_decode_batch keeps the device and pinned memory of its (sub-)batches in the context between calls (a

@@ -77,7 +77,7 @@ class CallStats(ctypes.Structure):
     _fields_ = [("upload_ms", ctypes.c_double), ("decode_ms", ctypes.c_double), ("download_ms", ctypes.c_double),
                 ("total_ms", ctypes.c_double), ("kernel_span_ms", ctypes.c_double), ("slot_occupancy", ctypes.c_double),
                 ("streams", ctypes.c_uint64), ("units", ctypes.c_uint64), ("wave_slots", ctypes.c_uint32),
-                ("sub_batches", ctypes.c_uint32), ("slices", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("sub_batches", ctypes.c_uint32), ("slices", ctypes.c_uint32), ("refetched", ctypes.c_uint32)]
 
 
 class XzBlock(ctypes.Structure):

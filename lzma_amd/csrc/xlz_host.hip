@@ -299,7 +299,9 @@ struct xlz_batch {
     std::vector<uint64_t> slice_pack_bytes;
     SlicePiece *d_pieces = nullptr; // all launches' tables, one after the other
     uint8_t *d_pack = nullptr;      // the packed image of one launch's pieces (xlz_gather_kernel), downloaded linearly
-    UnitResult *pin_res = nullptr;  // pinned: the unit results behind every launch (slice_fracs.size() x units)
+    UnitResult *d_res_snap = nullptr; // the unit results behind every launch (slice_fracs.size() x units): each launch
+                                      // writes d_results, a copy on the run stream keeps what launch k left there
+    UnitResult *pin_res = nullptr;    // pinned: the same on the host, fetched by download_sliced
     // heads first: the first launch starts when the first head_frac / 65536 (+ 4 KiB) of every unit's input is on the
     // device (LaunchParams.head_frac); the tails follow while it decodes.  The pinned image and the device staging range
     // are packed heads | tails; a scatter kernel puts each part into the input arena.
@@ -781,6 +783,7 @@ int batch_free(xlz_batch *b)
     batch_release(b, b->d_states);
     batch_release(b, b->d_pieces);
     batch_release(b, b->d_pack);
+    batch_release(b, b->d_res_snap);
     batch_release(b, b->pin_res, true);
     delete b;
     return XLZ_OK;
@@ -1126,6 +1129,7 @@ static int batch_create_ex(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t 
             if (hipEventCreateWithFlags(&b->slice_ev[k], hipEventDisableTiming) != hipSuccess) return fail(XLZ_ERR_DEVICE);
         if (!batch_alloc(b, &b->d_pieces, std::max<size_t>(total_pieces, 1) * sizeof(SlicePiece)) ||
             !batch_alloc(b, &b->d_pack, (size_t)max_pack + kArenaAlign) ||
+            !batch_alloc(b, &b->d_res_snap, (size_t)K * nu * sizeof(UnitResult)) ||
             !batch_alloc(b, &b->pin_res, (size_t)K * nu * sizeof(UnitResult), true))
             return fail(XLZ_ERR_DEVICE);
         size_t at = 0;
@@ -1242,6 +1246,9 @@ extern "C" int xlz_batch_run(xlz_batch *b)
                 p.slice_k = (uint32_t)k;
                 p.head_frac = k == 0 ? b->head_frac : 0;
                 if (launch_decode(p, ctx->num_cus, rs) != 0) return XLZ_ERR_DEVICE;
+                // (launch k + 1 writes the same results: download_sliced reads launch k's from this copy, queued in front of it)
+                HIP_TRY(hipMemcpyAsync(b->d_res_snap + k * b->units.size(), b->d_results, b->units.size() * sizeof(UnitResult),
+                                       hipMemcpyDeviceToDevice, rs));
                 HIP_TRY(hipEventRecord(b->slice_ev[k], rs));
             }
             if (b->head_frac) { // the pinned image is free again when the tails have left it
@@ -1765,6 +1772,23 @@ struct SlotClock {
 // fetched once more by the caller (xlz_batch::rewritten), and so are the streams in `gaps`: a unit of theirs fell short of
 // a launch's bound (its head ran out in the first launch, xlz_batch: head_frac) and produced the bytes up to it only
 // later, when that bound's pieces had gone out.  per_slice (optional): slot occupancy of every launch.
+//
+// The shipped library reads nothing from the environment here; a test build (-DXLZ_DEV_KNOBS, tests/test_gpu_pipeline.py)
+// takes XLZ_DEV_LATE_RESULTS=1: the copy stream fetches launch k's results only when launch k + 1 has ended too (its pieces
+// are packed behind launch k alone) -- the latest a download of results could run, every time.
+bool dev_late_results()
+{
+#ifdef XLZ_DEV_KNOBS
+    static const bool v = [] {
+        const char *e = getenv("XLZ_DEV_LATE_RESULTS");
+        return e && strcmp(e, "1") == 0;
+    }();
+    return v;
+#else
+    return false;
+#endif
+}
+
 int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<double> *per_slice, std::vector<size_t> &gaps)
 {
     xlz_ctx *ctx = b->ctx;
@@ -1782,13 +1806,15 @@ int download_sliced(xlz_batch *b, const xlz_stream_desc *streams, std::vector<do
     // in front of chunk j: every launch up to the one the chunk is of (behind the last chunk: all of them -- launches that
     // finish no byte still deliver their results) hands its unit results and its packed pieces to the copy stream
     size_t next_k = 0, piece_base = 0;
+    const bool late = dev_late_results();
     auto before = [&](size_t j, hipStream_t cs) {
         for (const size_t upto = j < chunks.size() ? chunks[j].k : K - 1; next_k <= upto; next_k++) {
             const size_t k = next_k;
             if (hipStreamWaitEvent(cs, b->slice_ev[k], 0) != hipSuccess ||
-                hipMemcpyAsync(b->pin_res + k * nu, b->d_results, nu * sizeof(UnitResult), hipMemcpyDeviceToHost, cs) != hipSuccess ||
                 launch_gather(b->d_pieces + piece_base, (uint32_t)b->slice_pieces[k].size(), b->d_out, b->d_pack,
-                              b->slice_pack_bytes[k], ctx->num_cus, cs) != 0)
+                              b->slice_pack_bytes[k], ctx->num_cus, cs) != 0 ||
+                (late && k + 1 < K && hipStreamWaitEvent(cs, b->slice_ev[k + 1], 0) != hipSuccess) ||
+                hipMemcpyAsync(b->pin_res + k * nu, b->d_res_snap + k * nu, nu * sizeof(UnitResult), hipMemcpyDeviceToHost, cs) != hipSuccess)
                 return false;
             piece_base += b->slice_pieces[k].size();
         }
@@ -2083,6 +2109,7 @@ extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, si
                     if (!again.empty()) e = download_all(b, streams + cuts[k], results + cuts[k], &again);
                 }
                 std::lock_guard<std::mutex> lk(mu);
+                if (e == XLZ_OK) cs.refetched += (uint32_t)again.size();
                 cs.slices = std::max<uint32_t>(cs.slices, (uint32_t)b->slice_fracs.size());
                 for (double o : occ) occ_busy += o * 1.0, occ_span += 1.0; // (weight: one launch = 1 ms; good enough for a mean)
             } else {

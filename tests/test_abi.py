@@ -97,3 +97,10 @@ def test_library_was_built_from_the_sources_in_the_tree(xlz_so):
     info = N.library_info()
     assert info["build_id"] == info["tree_source_id"] and info["built_from_tree"], info
     assert len(info["sha256"]) == 64 and not info["xlz_so_override"]
+
+
+def test_shipped_library_has_no_test_knobs(xlz_so):
+    """the knobs of a -DXLZ_DEV_KNOBS build (tests/test_gpu_pipeline.py: results read late) are not in the shipped library"""
+    with open(os.path.join(ROOT, "lzma_amd", "libxlz.so"), "rb") as f:
+        blob = f.read()
+    assert b"XLZ_DEV_LATE_RESULTS" not in blob and b"XLZ_STORED_UNIT_KIB" not in blob
