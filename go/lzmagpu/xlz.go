@@ -144,6 +144,7 @@ var (
 	errAlreadyClosed          = errors.New("lzma: already closed")
 	ErrDevice                 = errors.New("lzma: HIP device error")
 	ErrUnsupported            = errors.New("lzma: stream not supported by the GPU path")
+	ErrBadArgument            = errors.New("lzma: bad argument") // XLZ_ERR_BAD_ARG of a checked call: a range's stream, kind or reserved field
 )
 
 // readError maps a status of xlz_reader_read / a per-stream batch status onto the value the
@@ -630,6 +631,110 @@ func SetSlicing(minCallBytes, sliceBytes uint64, maxSlices uint32) error {
 		return ErrDevice
 	}
 	return nil
+}
+
+// Check ids of CheckRange.Kind: the .xz check ids (XLZ_CHECK_CRC32, XLZ_CHECK_CRC64).
+const (
+	CheckCRC32 = 1
+	CheckCRC64 = 4
+)
+
+// CheckRange names bytes [Off, Off+Len) of the output of stream Stream of a DecodeBatchChecked call (xlz_check_range); the
+// digest covers what the decoder produced of them.
+type CheckRange struct {
+	Stream   uint64
+	Off, Len uint64
+	Kind     uint32
+}
+
+// DecodeBatchChecked is DecodeBatch plus the CRC32 / CRC64 of ranges of the outputs, computed on the GPU where the decode
+// left the bytes, before the call's device memory is released (xlz_decode_batch_checked).  Not part of the reference,
+// which has no checks.  CRC32 digests are zero-extended.
+func DecodeBatchChecked(streams [][]byte, outs [][]byte, ranges []CheckRange) (lens []int, errs []error, digests []uint64, err error) {
+	c, err := context()
+	if err != nil {
+		return nil, nil, nil, err
+	}
+	n := len(streams)
+	descs := (*C.xlz_stream_desc)(C.calloc(C.size_t(n+1), C.size_t(unsafe.Sizeof(C.xlz_stream_desc{}))))
+	results := (*C.xlz_result)(C.calloc(C.size_t(n+1), C.size_t(unsafe.Sizeof(C.xlz_result{}))))
+	cr := (*C.xlz_check_range)(C.calloc(C.size_t(len(ranges)+1), C.size_t(unsafe.Sizeof(C.xlz_check_range{}))))
+	dg := (*C.uint64_t)(C.calloc(C.size_t(len(ranges)+1), 8))
+	defer C.free(unsafe.Pointer(descs))
+	defer C.free(unsafe.Pointer(results))
+	defer C.free(unsafe.Pointer(cr))
+	defer C.free(unsafe.Pointer(dg))
+	dv := unsafe.Slice(descs, n+1)
+	rv := unsafe.Slice(results, n+1)
+	for i := range streams {
+		dv[i].in, dv[i].in_len = cbuf(streams[i])
+		op, ol := cbuf(outs[i])
+		dv[i].out, dv[i].out_cap = op, ol
+		dv[i].format = C.XLZ_FMT_LZMA_ALONE
+	}
+	cv := unsafe.Slice(cr, len(ranges)+1)
+	for i, r := range ranges {
+		cv[i].stream, cv[i].off, cv[i].len, cv[i].kind = C.uint64_t(r.Stream), C.uint64_t(r.Off), C.uint64_t(r.Len), C.uint32_t(r.Kind)
+	}
+	if st := C.xlz_decode_batch_checked(c, descs, C.size_t(n), results, cr, C.size_t(len(ranges)), dg); st != C.XLZ_OK {
+		if st == C.XLZ_ERR_BAD_ARG {
+			return nil, nil, nil, ErrBadArgument
+		}
+		return nil, nil, nil, ErrDevice
+	}
+	lens = make([]int, n)
+	errs = make([]error, n)
+	for i := 0; i < n; i++ {
+		lens[i] = int(rv[i].out_len)
+		errs[i] = readError(rv[i].status)
+	}
+	digests = make([]uint64, len(ranges))
+	for i, d := range unsafe.Slice(dg, len(ranges)+1)[:len(ranges)] {
+		digests[i] = uint64(d)
+	}
+	return lens, errs, digests, nil
+}
+
+// CRC32Combine / CRC64Combine: the CRC of A followed by B from the CRCs of A and of B and len(B) (xlz_crc32_combine /
+// xlz_crc64_combine; host only) -- folds the digests of slices of one stream that were checked apart.
+func CRC32Combine(a, b uint32, lenB uint64) uint32 {
+	return uint32(C.xlz_crc32_combine(C.uint32_t(a), C.uint32_t(b), C.uint64_t(lenB)))
+}
+func CRC64Combine(a, b uint64, lenB uint64) uint64 {
+	return uint64(C.xlz_crc64_combine(C.uint64_t(a), C.uint64_t(b), C.uint64_t(lenB)))
+}
+
+// SetCheckMode says where DecodeXZ / Decode7z verify CRC32 / CRC64 (xlz_ctx_set_check_mode): 0 on host threads behind the
+// download (the default), 1 on the GPU next to the decode.  The outcome of a call does not depend on it.
+func SetCheckMode(mode int) error {
+	c, err := context()
+	if err != nil {
+		return err
+	}
+	if st := C.xlz_ctx_set_check_mode(c, C.int(mode)); st != C.XLZ_OK {
+		return ErrBadArgument
+	}
+	return nil
+}
+
+// CheckStats is xlz_check_stats: who checked what in the last checked call.
+type CheckStats struct {
+	DeviceRanges, DeviceBytes, HostRanges, HostBytes, EmptyRanges uint64
+	KernelMs                                                        float64
+	Launches                                                        uint32
+}
+
+func LastCheckStats() (CheckStats, error) {
+	c, err := context()
+	if err != nil {
+		return CheckStats{}, err
+	}
+	var s C.xlz_check_stats
+	if st := C.xlz_ctx_last_check_stats(c, &s); st != C.XLZ_OK {
+		return CheckStats{}, ErrDevice
+	}
+	return CheckStats{uint64(s.device_ranges), uint64(s.device_bytes), uint64(s.host_ranges), uint64(s.host_bytes), uint64(s.empty_ranges),
+		float64(s.kernel_ms), uint32(s.launches)}, nil
 }
 
 // Trim gives back the device and pinned memory the context keeps between DecodeBatch calls (xlz_ctx_trim): a call of the

@@ -261,6 +261,55 @@ int xlz_batch_launch_info(xlz_batch *batch, uint32_t *workgroups, uint32_t *lds_
 const char *xlz_batch_kernel_name(xlz_batch *batch);
 void xlz_batch_destroy(xlz_batch *batch);
 
+/* ---- integrity checks on the device ----------------------------------------------------------
+ * Outside the reference (which has no checks).  CRC32 (IEEE 802.3, reflected 0xEDB88320: .xz check 1, .7z) and CRC64
+ * (.xz check 4, reflected 0xC96C5795D7870F42) of RANGES of the decoded output, computed by HIP kernels on the bytes where
+ * the decode left them in HBM (lzma_amd/csrc/xlz_check_dev.hip): a caller that keeps the output on
+ * the GPU verifies it without downloading it, and a host-to-host call gets its digests before its arenas go back to the
+ * pool.  A range's digest covers [off, off + len) of its stream's output cut to [0, out_len) -- what the decoder produced
+ * of it; an empty intersection gives 0, the CRC of no bytes.  Digests are the published CRCs (what zlib.crc32 and liblzma
+ * give), CRC32 zero-extended to 64 bits.                                                              */
+enum { XLZ_CHECK_NONE = 0, XLZ_CHECK_CRC32 = 1, XLZ_CHECK_CRC64 = 4 }; /* the .xz check ids */
+typedef struct xlz_check_range {
+    uint64_t stream;   /* index into the call's / the batch's streams; >= n: XLZ_ERR_BAD_ARG for the call */
+    uint64_t off, len; /* bytes of THAT STREAM'S OUTPUT                                               */
+    uint32_t kind;     /* XLZ_CHECK_CRC32 / XLZ_CHECK_CRC64, else XLZ_ERR_BAD_ARG                       */
+    uint32_t reserved; /* 0, else XLZ_ERR_BAD_ARG                                                      */
+} xlz_check_range;
+/* Device-resident: waits for and collects the latest run like xlz_batch_results, runs the check kernels on the batch's
+ * stream and fetches the n digests; nothing else leaves the device.  Ranges may overlap and come in any order.      */
+int xlz_batch_checks(xlz_batch *batch, const xlz_check_range *ranges, size_t n, uint64_t *digests);
+/* xlz_decode_batch plus the digests of n_ranges ranges, computed on the device behind every (sub-)batch's results, in all
+ * three forms of the pipeline (xlz_decode_batch_plan).  Streams that never sit in an arena (4 GiB and more; streams that
+ * failed on the host) get theirs from the host's code over the caller's buffer (xlz_check_stats.host_ranges).        */
+int xlz_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                             const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests);
+/* crc(A || B) from crc(A), crc(B) and the length of B: host only, no device needed.  What folds the digests of the slices
+ * of one stream that were checked apart (several GPUs, several calls).                                   */
+uint32_t xlz_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+uint64_t xlz_crc64_combine(uint64_t crc_a, uint64_t crc_b, uint64_t len_b);
+/* Where xlz_xz_decode / xlz_7z_decode verify.  0 (default): on host threads after the call's download, as ever.  1: every
+ * CRC32 / CRC64 block, folder and file (per-file ranges inside solid folders) through xlz_decode_batch_checked, digests
+ * compared on the host; SHA-256 blocks, reserved check types and .7z Copy folders (never on the device) stay on the host.
+ * Bytes, status and *unverified are the same in both modes.  xlz_xz_decode_multi / xlz_7z_decode_multi ignore the mode:
+ * they check on the host.  Any other value: XLZ_ERR_BAD_ARG.                                              */
+int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode);
+int xlz_ctx_check_mode(const xlz_ctx *ctx);
+/* Of the most recent xlz_batch_checks / xlz_decode_batch_checked on `ctx`, or of the most recent xlz_xz_decode /
+ * xlz_7z_decode in check mode 1 (summed over the batches it made): who checked what.                      */
+typedef struct xlz_check_stats {
+    uint64_t device_ranges; /* ranges whose bytes the check kernels read ...                              */
+    uint64_t device_bytes;  /* ... and how many bytes that was                                             */
+    uint64_t host_ranges;   /* ranges the host's code checked (streams outside the arenas; the front-ends' SHA-256
+                               blocks and Copy folders)                                                     */
+    uint64_t host_bytes;
+    uint64_t empty_ranges;  /* ranges with nothing to check: no byte of them was produced                  */
+    double kernel_ms;       /* the check kernels by HIP events, summed over the launches                   */
+    uint32_t launches;      /* (sub-)batches that ran check kernels                                        */
+    uint32_t reserved;
+} xlz_check_stats;
+int xlz_ctx_last_check_stats(xlz_ctx *ctx, xlz_check_stats *out);
+
 /* ---- pull-style readers mirroring the reference's Go surface --------------- */
 /* Constructors take the compressed stream as a buffer (a Go shim slurps its io.Reader
  * first) and copy it.  Constructor-time errors are the ones the reference's

@@ -12,7 +12,8 @@ from . import _native as N
 from ._native import (EOF, ERR_BAD_ARG, ERR_CLOSED, ERR_DEVICE, ERR_HEADER_EOF,  # noqa: F401
                       ERR_INSUFFICIENT_PROPS, ERR_NEED_ONE_READER, ERR_OUT_CAP, ERR_PROPS,
                       ERR_RC_INIT, ERR_RESULT, ERR_UNEXPECTED_EOF, ERR_UNSUPPORTED,
-                      FMT_LZMA2_RAW, FMT_LZMA_ALONE, FMT_LZMA_RAW, NEED_INPUT, OK, OK_INPUT_EOF, UNKNOWN_SIZE)
+                      FMT_LZMA2_RAW, FMT_LZMA_ALONE, FMT_LZMA_RAW, NEED_INPUT, OK, OK_INPUT_EOF, UNKNOWN_SIZE,
+                      CHECK_CRC32, CHECK_CRC64, CHECK_NONE)
 
 
 class LzmaError(Exception):
@@ -99,6 +100,25 @@ class Context:
             raise LzmaError(st, "xlz_ctx_trim")
         return n.value
 
+    def set_check_mode(self, mode):
+        """where xz_decode / sevenzip_decode verify CRC32 / CRC64 (xlz_ctx_set_check_mode): 0 on host threads behind the
+        download (default), 1 on the device next to the decode"""
+        st = N.lib().xlz_ctx_set_check_mode(self._h, int(mode))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_set_check_mode")
+
+    def check_mode(self):
+        return N.lib().xlz_ctx_check_mode(self._h)
+
+    def last_check_stats(self):
+        """who checked what in the last Batch.checks / decode_batch_checked / front-end call in check mode 1 on this
+        context (xlz_ctx_last_check_stats) -> dict"""
+        cs = N.CheckStats()
+        st = N.lib().xlz_ctx_last_check_stats(self._h, ctypes.byref(cs))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_check_stats")
+        return {k: getattr(cs, k) for k, _ in N.CheckStats._fields_ if k != "reserved"}
+
     def event_record(self, slot):
         st = N.lib().xlz_ctx_event_record(self._h, slot)
         if st != OK:
@@ -161,6 +181,41 @@ def decode_batch(ctx, streams):
         raise LzmaError(st, "xlz_decode_batch")
     del keep
     return [(outs[i].raw[: res[i].out_len], res[i].status, res[i].in_consumed) for i in range(n)]
+
+
+def _make_ranges(ranges):
+    """[(stream, off, len, kind), ...] -> (xlz_check_range array, digest array)"""
+    n = len(ranges)
+    arr = (N.CheckRange * max(n, 1))()
+    for q, (stream, off, length, kind) in enumerate(ranges):
+        arr[q].stream, arr[q].off, arr[q].len, arr[q].kind = int(stream), int(off), int(length), int(kind)
+    return arr, (ctypes.c_uint64 * max(n, 1))()
+
+
+def decode_batch_checked(ctx, streams, checks):
+    """decode_batch plus the CRC32 / CRC64 of ranges of the outputs, computed on the GPU before the call's device memory is
+    released (xlz_decode_batch_checked).  checks: [(stream index, off, len, CHECK_CRC32 | CHECK_CRC64), ...]; a range
+    covers what the decoder produced of it.  -> (list of (output bytes, status, in_consumed), list of digests)"""
+    streams, checks = list(streams), list(checks)
+    n = len(streams)
+    descs, keep, outs = _make_descs(streams)
+    res = (N.Result * max(n, 1))()
+    arr, dig = _make_ranges(checks)
+    st = N.lib().xlz_decode_batch_checked(ctx._h, descs, n, res, arr, len(checks), dig)
+    if st != OK:
+        raise LzmaError(st, "xlz_decode_batch_checked")
+    del keep
+    return [(outs[i].raw[: res[i].out_len], res[i].status, res[i].in_consumed) for i in range(n)], list(dig[: len(checks)])
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """CRC32 of A + B from the CRC32s of A and of B and len(B) (xlz_crc32_combine; host only)"""
+    return N.lib().xlz_crc32_combine(crc_a, crc_b, len_b)
+
+
+def crc64_combine(crc_a, crc_b, len_b):
+    """CRC64 (the .xz one) of A + B from the CRC64s of A and of B and len(B) (xlz_crc64_combine; host only)"""
+    return N.lib().xlz_crc64_combine(crc_a, crc_b, len_b)
 
 
 def decode_batch_plan(out_caps):
@@ -295,6 +350,16 @@ class Batch:
         if st != OK:
             raise LzmaError(st, "xlz_batch_unit_trace")
         return a[: n.value], b[: n.value], c[: n.value]
+
+    def checks(self, ranges):
+        """CRC32 / CRC64 of ranges of the decoded outputs, computed on the device; only the digests come back
+        (xlz_batch_checks).  ranges: [(stream index, off, len, CHECK_CRC32 | CHECK_CRC64), ...] -> list of digests"""
+        ranges = list(ranges)
+        arr, dig = _make_ranges(ranges)
+        st = N.lib().xlz_batch_checks(self._h, arr, len(ranges), dig)
+        if st != OK:
+            raise LzmaError(st, "xlz_batch_checks")
+        return list(dig[: len(ranges)])
 
     def download(self, i, length):
         buf = ctypes.create_string_buffer(max(int(length), 1))

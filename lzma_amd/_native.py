@@ -34,6 +34,10 @@ FMT_LZMA2_RAW = 2
 
 UNKNOWN_SIZE = 0xFFFFFFFFFFFFFFFF
 
+CHECK_NONE = 0
+CHECK_CRC32 = 1
+CHECK_CRC64 = 4
+
 # every symbol include/xlz.h declares (tests check the .so exports all of them)
 EXPORTS = [
     "xlz_version", "xlz_build_id", "xlz_kernel_id", "xlz_strerror", "xlz_device_count", "xlz_decode_prop", "xlz_decode_dict_size",
@@ -46,6 +50,8 @@ EXPORTS = [
     "xlz_reader_read", "xlz_reader_close", "xlz_reader_free", "xlz_xz_index", "xlz_xz_decode",
     "xlz_decode_batch_multi", "xlz_decode_batch_multi_plan", "xlz_xz_decode_multi", "xlz_7z_decode_multi", "xlz_batch_unit_trace", "xlz_reader_stats", "xlz_reader_memory", "xlz_batch_advice", "xlz_batch_launch_info", "xlz_reader_reset", "xlz_reader_reopen", "xlz_reader_expect_more", "xlz_reader_feed", "xlz_reader_feed_eof", "xlz_7z_index", "xlz_7z_decode",
     "xlz_lzma2_units", "xlz_ctx_set_slicing", "xlz_ctx_trim", "xlz_batch_kernel_name", "xlz_decode_batch_plan",
+    "xlz_batch_checks", "xlz_decode_batch_checked", "xlz_crc32_combine", "xlz_crc64_combine", "xlz_ctx_set_check_mode",
+    "xlz_ctx_check_mode", "xlz_ctx_last_check_stats",
 ]
 
 
@@ -78,6 +84,17 @@ class CallStats(ctypes.Structure):
                 ("total_ms", ctypes.c_double), ("kernel_span_ms", ctypes.c_double), ("slot_occupancy", ctypes.c_double),
                 ("streams", ctypes.c_uint64), ("units", ctypes.c_uint64), ("wave_slots", ctypes.c_uint32),
                 ("sub_batches", ctypes.c_uint32), ("slices", ctypes.c_uint32), ("refetched", ctypes.c_uint32)]
+
+
+class CheckRange(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint64), ("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("kind", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class CheckStats(ctypes.Structure):
+    _fields_ = [("device_ranges", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_ranges", ctypes.c_uint64),
+                ("host_bytes", ctypes.c_uint64), ("empty_ranges", ctypes.c_uint64), ("kernel_ms", ctypes.c_double),
+                ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class XzBlock(ctypes.Structure):
@@ -194,6 +211,16 @@ def lib():
     L.xlz_ctx_trim.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.xlz_decode_batch_plan.argtypes = [ctypes.POINTER(StreamDesc), sz, ctypes.POINTER(sz), sz, ctypes.POINTER(sz), ctypes.POINTER(i32)]
     L.xlz_batch_kernel_name.argtypes = [vp]
+    L.xlz_batch_checks.argtypes = [vp, ctypes.POINTER(CheckRange), sz, ctypes.POINTER(ctypes.c_uint64)]
+    L.xlz_decode_batch_checked.argtypes = [vp, ctypes.POINTER(StreamDesc), sz, ctypes.POINTER(Result), ctypes.POINTER(CheckRange), sz,
+                                           ctypes.POINTER(ctypes.c_uint64)]
+    L.xlz_crc32_combine.restype = ctypes.c_uint32
+    L.xlz_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+    L.xlz_crc64_combine.restype = ctypes.c_uint64
+    L.xlz_crc64_combine.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]
+    L.xlz_ctx_set_check_mode.argtypes = [vp, i32]
+    L.xlz_ctx_check_mode.argtypes = [vp]
+    L.xlz_ctx_last_check_stats.argtypes = [vp, ctypes.POINTER(CheckStats)]
     L.xlz_batch_kernel_name.restype = ctypes.c_char_p
     L.xlz_batch_create.argtypes = [vp, ctypes.POINTER(StreamDesc), sz, ctypes.POINTER(vp)]
     L.xlz_batch_run.argtypes = [vp]

@@ -21,6 +21,7 @@
 
 #include "../../include/xlz.h"
 #include "xlz_check.h"
+#include "xlz_check_host.h"
 
 namespace {
 
@@ -383,7 +384,40 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
         which.push_back(i);
     }
     std::vector<xlz_result> r(d.size());
-    if (!d.empty()) {
+    // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 of every file and folder that the batch decodes comes
+    // from the device with the batch's results -- per-file ranges inside solid folders --, in the order the loop below
+    // asks for them: dg[dg_first[i] ...] = folder i's files that carry a CRC, then the folder's own
+    const bool dev = verify && n_ctx <= 1 && ctx && xlz_ctx_check_mode(ctx) == 1;
+    std::vector<uint64_t> dg;
+    std::vector<size_t> dg_first(fo.size(), 0);
+    if (dev) {
+        std::vector<xlz_check_range> cr;
+        for (size_t k = 0; k < which.size(); k++) {
+            const xlz_7z_folder &f = fo[which[k]];
+            dg_first[which[k]] = cr.size();
+            xlz_check_range c;
+            memset(&c, 0, sizeof c);
+            c.stream = k, c.kind = XLZ_CHECK_CRC32;
+            uint64_t o = 0;
+            for (uint32_t j = 0; j < f.n_substreams; j++) {
+                const xlz_7z_substream &ss = subs[f.first_substream + j];
+                if (ss.has_crc) {
+                    c.off = o, c.len = ss.size;
+                    cr.push_back(c);
+                }
+                o += ss.size;
+            }
+            if (f.has_crc) {
+                c.off = 0, c.len = f.unpack_len;
+                cr.push_back(c);
+            }
+        }
+        dg.resize(cr.size());
+        if (!d.empty()) {
+            int st = xlz_internal_decode_batch_checked(ctx, d.data(), d.size(), r.data(), cr.data(), cr.size(), dg.data(), 1);
+            if (st != XLZ_OK) return st;
+        }
+    } else if (!d.empty()) {
         int st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), d.size(), r.data())
                            : xlz_decode_batch(ctx, d.data(), d.size(), r.data());
         if (st != XLZ_OK) return st;
@@ -402,17 +436,19 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
                 const xlz_7z_folder &f = fo[i];
                 uint64_t o = f.unpack_off;
                 bool any = false;
+                const bool on_dev = dev && f.method != XLZ_7Z_COPY; // (Copy folders never were on the device)
+                size_t q = dg_first[i];
                 for (uint32_t k = 0; k < f.n_substreams; k++) {
                     const xlz_7z_substream &ss = subs[f.first_substream + k];
                     if (ss.has_crc) {
                         any = true;
-                        if (xlzcheck::crc32(out + o, (size_t)ss.size) != ss.crc) bad[i] = 1;
+                        if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(out + o, (size_t)ss.size)) != ss.crc) bad[i] = 1;
                     }
                     o += ss.size;
                 }
                 if (f.has_crc) {
                     any = true;
-                    if (xlzcheck::crc32(out + f.unpack_off, (size_t)f.unpack_len) != f.crc) bad[i] = 1;
+                    if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(out + f.unpack_off, (size_t)f.unpack_len)) != f.crc) bad[i] = 1;
                 }
                 if (!any && !bad[i]) bad[i] = 2;
             }
@@ -421,6 +457,14 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
         for (unsigned t = 1; t < nth; t++) th.emplace_back(work, t);
         work(0);
         for (auto &x : th) x.join();
+        if (dev)
+            for (const xlz_7z_folder &f : fo) {
+                if (f.method != XLZ_7Z_COPY) continue;
+                uint64_t nr = f.has_crc, nbytes = f.has_crc ? f.unpack_len : 0;
+                for (uint32_t k = 0; k < f.n_substreams; k++)
+                    if (subs[f.first_substream + k].has_crc) nr++, nbytes += subs[f.first_substream + k].size;
+                if (nr) xlz_internal_check_stats_host(ctx, nr, nbytes);
+            }
         for (int b : bad) {
             if (b == 1) return XLZ_ERR_RESULT;
             nu += b == 2;
@@ -550,6 +594,7 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     if (!file || (!out && out_cap) || !out_len) return XLZ_ERR_BAD_ARG;
     *out_len = 0;
     if (unverified) *unverified = 0;
+    if (verify && n_ctx == 1 && xlz_ctx_check_mode(ctx) == 1) xlz_internal_check_stats_reset(ctx); // (an encoded header's batch counts too)
     Streams s;
     std::vector<uint8_t> dh;
     int st = main_streams(ctx, file, len, s, dh);

@@ -27,6 +27,9 @@
 
 #include "../../include/xlz.h"
 #include "xlz_format.h"
+#include "xlz_check.h"
+#include "xlz_check_dev.h"
+#include "xlz_check_host.h"
 
 using namespace xlz;
 
@@ -234,6 +237,12 @@ struct xlz_ctx {
     // xlz_ctx_set_slicing: when a call of one wave round runs as a sequence of launches, and as how many
     uint64_t sliced_call_bytes = kSlicedCallBytes, slice_bytes = kSliceBytes;
     uint32_t max_slices = kMaxSlices;
+    // device checks (xlz_check_dev.hip): the row-step tables and constants of CRC32 [0] and CRC64 [1] on the device (made
+    // by the first check), the stream the checks of xlz_decode_batch_checked's sub-batches run on, xlz_ctx_set_check_mode
+    void *chk_tab[2] = {}, *chk_consts[2] = {};
+    hipStream_t check_stream = nullptr;
+    int check_mode = 0;
+    xlz_check_stats last_check = {}; // xlz_ctx_last_check_stats
 };
 
 // per-stream bookkeeping of a batch
@@ -311,6 +320,11 @@ struct xlz_batch {
     hipEvent_t ev_heads = nullptr, ev_tails = nullptr;
     std::function<int()> upload_tails; // pending second half of the upload, run by xlz_batch_run behind the first launch
     PinLease in_lease;
+    // xlz_batch_checks / xlz_decode_batch_checked: range table | segment values | digests on the device, range table |
+    // digests in pinned memory (grow-only, kept until the batch goes), and the events around the check kernels
+    uint8_t *d_chk = nullptr, *pin_chk = nullptr;
+    size_t d_chk_cap = 0, pin_chk_cap = 0;
+    hipEvent_t chk_ev0 = nullptr, chk_ev1 = nullptr;
 };
 
 // ---------------------------------------------------------------- helpers ----
@@ -455,6 +469,11 @@ extern "C" void xlz_ctx_destroy(xlz_ctx *c)
     if (c->queue) (void)hipFree(c->queue);
     if (c->queue2) (void)hipFree(c->queue2);
     if (c->prio_tab) (void)hipFree(c->prio_tab);
+    for (int k = 0; k < 2; k++) {
+        if (c->chk_tab[k]) (void)hipFree(c->chk_tab[k]);
+        if (c->chk_consts[k]) (void)hipFree(c->chk_consts[k]);
+    }
+    if (c->check_stream) (void)hipStreamDestroy(c->check_stream);
     if (c->pipe.pin_in) (void)hipHostFree(c->pipe.pin_in);
     for (int i = 0; i < HostPipe::kRing; i++) {
         if (c->pipe.ring[i]) (void)hipHostFree(c->pipe.ring[i]);
@@ -785,6 +804,10 @@ int batch_free(xlz_batch *b)
     batch_release(b, b->d_pack);
     batch_release(b, b->d_res_snap);
     batch_release(b, b->pin_res, true);
+    batch_release(b, b->d_chk);
+    batch_release(b, b->pin_chk, true);
+    if (b->chk_ev0) (void)hipEventDestroy(b->chk_ev0);
+    if (b->chk_ev1) (void)hipEventDestroy(b->chk_ev1);
     delete b;
     return XLZ_OK;
 }
@@ -1596,6 +1619,220 @@ extern "C" int xlz_batch_download(xlz_batch *b, size_t i, uint8_t *dst, size_t l
 
 extern "C" void xlz_batch_destroy(xlz_batch *b) { batch_free(b); }
 
+// ---------------------------------------------------------------- checks on the device ----
+namespace xlz {
+int check_launch(int width, const uint8_t *arena, const xlzchk::DevRange *ranges, uint32_t n_ranges, uint32_t total_segs,
+                 const void *tab, const void *consts, uint64_t *seg_vals, uint64_t *digests, int num_cus, hipStream_t stream);
+}
+
+namespace {
+
+// the constants of both CRCs on the host: the exported combine, and what the first check of a context uploads
+struct CheckHost {
+    xlzchk::Consts<32> c32;
+    xlzchk::Consts<64> c64;
+    CheckHost()
+    {
+        xlzchk::build_consts<32>(c32);
+        xlzchk::build_consts<64>(c64);
+    }
+};
+const CheckHost &check_host()
+{
+    static const CheckHost h;
+    return h;
+}
+
+// (ctx->mu held) the tables and constants of both CRCs on the device, made by the context's first check
+int check_tables(xlz_ctx *ctx)
+{
+    if (ctx->chk_tab[0]) return XLZ_OK;
+    const CheckHost &h = check_host();
+    std::vector<uint32_t> t32(xlzchk::kTabEntries);
+    std::vector<uint64_t> t64(xlzchk::kTabEntries);
+    xlzchk::build_tables<32>(h.c32, t32.data());
+    xlzchk::build_tables<64>(h.c64, t64.data());
+    void *p[4] = {};
+    const void *src[4] = {t32.data(), t64.data(), &h.c32, &h.c64};
+    const size_t bytes[4] = {t32.size() * 4, t64.size() * 8, sizeof h.c32, sizeof h.c64};
+    bool ok = true;
+    for (int k = 0; k < 4 && ok; k++)
+        ok = hipMalloc(&p[k], bytes[k]) == hipSuccess && hipMemcpy(p[k], src[k], bytes[k], hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (void *q : p)
+            if (q) (void)hipFree(q);
+        return XLZ_ERR_DEVICE;
+    }
+    ctx->chk_tab[0] = p[0], ctx->chk_tab[1] = p[1], ctx->chk_consts[0] = p[2], ctx->chk_consts[1] = p[3];
+    return XLZ_OK;
+}
+
+int check_args(const xlz_check_range *ranges, size_t n_ranges, size_t n_streams, const uint64_t *digests)
+{
+    if ((!ranges || !digests) && n_ranges) return XLZ_ERR_BAD_ARG;
+    for (size_t q = 0; q < n_ranges; q++)
+        if (ranges[q].stream >= n_streams || (ranges[q].kind != XLZ_CHECK_CRC32 && ranges[q].kind != XLZ_CHECK_CRC64) || ranges[q].reserved)
+            return XLZ_ERR_BAD_ARG;
+    return XLZ_OK;
+}
+
+uint64_t host_digest(uint32_t kind, const uint8_t *p, uint64_t n)
+{
+    return kind == XLZ_CHECK_CRC32 ? (uint64_t)xlzcheck::crc32(p, (size_t)n) : xlzcheck::crc64(p, (size_t)n);
+}
+
+// The digests of ranges[idx[0 .. n_idx)] (idx == nullptr: of ranges[0 .. n_idx)) of a COLLECTED batch, whose stream
+// `stream_base` is the batch's first: the ranges of streams in the output arena by the check kernels, queued on `stream`
+// -- the batch's own, or any other: collect() has waited for everything that writes the arena, its re-runs included --
+// and waited for.  digests[] is indexed like ranges[].  Streams marked oversize are skipped (xlz_decode_batch settles them
+// behind its batches); other streams outside the arena are checked on the host over `streams` (the batch's descriptors)
+// when given.
+int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *idx, size_t n_idx, size_t stream_base, uint64_t *digests,
+                     hipStream_t stream, const xlz_stream_desc *streams, xlz_check_stats &acc)
+{
+    using xlzchk::DevRange;
+    if (!n_idx) return XLZ_OK;
+    std::vector<DevRange> dev[2]; // CRC32, CRC64
+    std::vector<size_t> where[2]; // ... and the index of each one's digest
+    uint64_t segs[2] = {0, 0}, dev_bytes = 0;
+    for (size_t q = 0; q < n_idx; q++) {
+        const size_t ri = idx ? idx[q] : q;
+        const xlz_check_range &r = ranges[ri];
+        const size_t s = (size_t)(r.stream - stream_base);
+        const StreamPlan &pl = b->plans[s];
+        if (pl.oversize) continue;
+        const bool in_arena = pl.host_status == 1;
+        const uint64_t produced = in_arena ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : b->final_results[s].out_len;
+        const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
+        digests[ri] = 0;
+        if (hi == lo) {
+            acc.empty_ranges++;
+        } else if (!in_arena) {
+            if (streams && streams[s].out && hi <= streams[s].out_cap) {
+                digests[ri] = host_digest(r.kind, streams[s].out + lo, hi - lo);
+                acc.host_ranges++, acc.host_bytes += hi - lo;
+            } else {
+                acc.empty_ranges++;
+            }
+        } else {
+            const int k = r.kind == XLZ_CHECK_CRC64;
+            DevRange d;
+            d.off = pl.out_off + lo, d.len = hi - lo;
+            const uint64_t ns = xlzchk::range_segments(d.off, d.len);
+            if (d.off + d.len > b->out_bytes || segs[k] + ns > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+            d.seg_first = (uint32_t)segs[k], d.n_segs = (uint32_t)ns, d.out_index = (uint32_t)where[0].size() + (uint32_t)where[1].size(), d.reserved = 0;
+            segs[k] += ns;
+            dev[k].push_back(d);
+            where[k].push_back(ri);
+            dev_bytes += d.len;
+        }
+    }
+    const size_t n_dev = dev[0].size() + dev[1].size();
+    if (!n_dev) return XLZ_OK;
+    if (n_dev > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+    xlz_ctx *ctx = b->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    int st = check_tables(ctx);
+    if (st != XLZ_OK) return st;
+    // device: range table | segment values | digests; pinned: range table | digests
+    const size_t tab_bytes = n_dev * sizeof(DevRange), seg_bytes = (size_t)(segs[0] + segs[1]) * 8, dig_bytes = n_dev * 8;
+    if (b->d_chk_cap < tab_bytes + seg_bytes + dig_bytes) {
+        batch_release(b, b->d_chk);
+        b->d_chk = nullptr, b->d_chk_cap = 0;
+        const size_t want = tab_bytes + seg_bytes + dig_bytes;
+        if (!batch_alloc(b, &b->d_chk, want)) return XLZ_ERR_DEVICE;
+        b->d_chk_cap = want;
+    }
+    if (b->pin_chk_cap < tab_bytes + dig_bytes) {
+        batch_release(b, b->pin_chk, true);
+        b->pin_chk = nullptr, b->pin_chk_cap = 0;
+        if (!batch_alloc(b, &b->pin_chk, tab_bytes + dig_bytes, true)) return XLZ_ERR_DEVICE;
+        b->pin_chk_cap = tab_bytes + dig_bytes;
+    }
+    if (!b->chk_ev0) HIP_TRY(hipEventCreate(&b->chk_ev0));
+    if (!b->chk_ev1) HIP_TRY(hipEventCreate(&b->chk_ev1));
+    DevRange *h_tab = reinterpret_cast<DevRange *>(b->pin_chk);
+    uint64_t *h_dig = reinterpret_cast<uint64_t *>(b->pin_chk + tab_bytes);
+    if (!dev[0].empty()) memcpy(h_tab, dev[0].data(), dev[0].size() * sizeof(DevRange));
+    if (!dev[1].empty()) memcpy(h_tab + dev[0].size(), dev[1].data(), dev[1].size() * sizeof(DevRange));
+    DevRange *d_tab = reinterpret_cast<DevRange *>(b->d_chk);
+    uint64_t *d_seg = reinterpret_cast<uint64_t *>(b->d_chk + tab_bytes);
+    uint64_t *d_dig = reinterpret_cast<uint64_t *>(b->d_chk + tab_bytes + seg_bytes);
+    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(b->chk_ev0, stream));
+    if (xlz::check_launch(32, b->d_out, d_tab, (uint32_t)dev[0].size(), (uint32_t)segs[0], ctx->chk_tab[0], ctx->chk_consts[0], d_seg, d_dig,
+                          ctx->num_cus, stream) != 0 ||
+        xlz::check_launch(64, b->d_out, d_tab + dev[0].size(), (uint32_t)dev[1].size(), (uint32_t)segs[1], ctx->chk_tab[1], ctx->chk_consts[1],
+                          d_seg + segs[0], d_dig, ctx->num_cus, stream) != 0) {
+        if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the check kernels failed\n");
+        (void)hipStreamSynchronize(stream);
+        return XLZ_ERR_DEVICE;
+    }
+    HIP_TRY(hipEventRecord(b->chk_ev1, stream));
+    HIP_TRY(hipMemcpyAsync(h_dig, d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, b->chk_ev0, b->chk_ev1));
+    for (int k = 0; k < 2; k++)
+        for (size_t j = 0; j < dev[k].size(); j++) digests[where[k][j]] = h_dig[dev[k][j].out_index];
+    acc.device_ranges += n_dev, acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches++;
+    return XLZ_OK;
+}
+
+} // namespace
+
+extern "C" int xlz_batch_checks(xlz_batch *b, const xlz_check_range *ranges, size_t n, uint64_t *digests)
+{
+    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
+    int st = check_args(ranges, n, b->n, digests);
+    if (st != XLZ_OK) return st;
+    st = collect(b);
+    if (st != XLZ_OK) return st;
+    xlz_check_stats acc;
+    memset(&acc, 0, sizeof acc);
+    st = batch_checks_run(b, ranges, nullptr, n, 0, digests, b->run_stream ? b->run_stream : b->ctx->stream, nullptr, acc);
+    if (st != XLZ_OK) return st;
+    std::lock_guard<std::mutex> lock(b->ctx->mu);
+    b->ctx->last_check = acc;
+    return XLZ_OK;
+}
+
+extern "C" uint32_t xlz_crc32_combine(uint32_t a, uint32_t b, uint64_t len_b)
+{
+    return (uint32_t)xlzchk::combine<32>(check_host().c32, a, b, len_b);
+}
+extern "C" uint64_t xlz_crc64_combine(uint64_t a, uint64_t b, uint64_t len_b) { return xlzchk::combine<64>(check_host().c64, a, b, len_b); }
+
+extern "C" int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode)
+{
+    if (!ctx || (mode != 0 && mode != 1)) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->check_mode = mode;
+    return XLZ_OK;
+}
+extern "C" int xlz_ctx_check_mode(const xlz_ctx *ctx) { return ctx ? ctx->check_mode : XLZ_ERR_BAD_ARG; }
+
+extern "C" int xlz_ctx_last_check_stats(xlz_ctx *ctx, xlz_check_stats *out)
+{
+    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *out = ctx->last_check;
+    return XLZ_OK;
+}
+
+void xlz_internal_check_stats_reset(xlz_ctx *ctx)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    memset(&ctx->last_check, 0, sizeof ctx->last_check);
+}
+void xlz_internal_check_stats_host(xlz_ctx *ctx, uint64_t ranges, uint64_t bytes)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_check.host_ranges += ranges, ctx->last_check.host_bytes += bytes;
+}
+
 namespace {
 
 // Moves n chunks from the device to the callers' buffers through the context's pinned ring (one download at a time per
@@ -1973,11 +2210,15 @@ extern "C" int xlz_decode_batch_plan(const xlz_stream_desc *streams, size_t n, s
     return max_cuts && c.size() > max_cuts ? XLZ_ERR_OUT_CAP : XLZ_OK;
 }
 
-extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results)
+// xlz_decode_batch (n_ranges == 0) and xlz_decode_batch_checked: the digests of `ranges` are computed on the device behind
+// the results of every (sub-)batch, while its arenas are still the call's
+static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const xlz_check_range *ranges,
+                             size_t n_ranges, uint64_t *digests, bool accumulate)
 {
     if (!ctx || (!streams && n) || (!results && n)) return XLZ_ERR_BAD_ARG;
     for (size_t i = 0; i < n; i++)
         if (!streams[i].out && streams[i].out_cap) return XLZ_ERR_BAD_ARG;
+    if (check_args(ranges, n_ranges, n, digests) != XLZ_OK) return XLZ_ERR_BAD_ARG;
     // upload (pinned image, one copy) -> decode -> download (pinned ring, D2H overlapped with the scatter into the
     // callers' buffers).  A call of several wave rounds runs as a PIPELINE of sub-batches on three host threads:
     // sub-batch k+1 is parsed, packed and uploaded and sub-batch k-1 is downloaded and scattered while sub-batch k
@@ -2012,6 +2253,21 @@ extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, si
         for (size_t i = cuts[k]; i < cuts[k + 1]; i++) total += streams[i].out_cap;
         return total >= sliced_call_bytes ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_slices, total / slice_bytes)) : 1u;
     };
+
+    // checked calls: the ranges of every sub-batch, and the stream their kernels run on -- one of the context's own, not
+    // the sub-batch's: in the forms that queue the next piece's launches before this piece's results are read, a check
+    // on the same stream would wait for that piece's decode (collect() has waited for all that writes the bytes)
+    std::vector<std::vector<size_t>> sub_ranges(n_ranges ? S : 0);
+    xlz_check_stats chk;
+    memset(&chk, 0, sizeof chk);
+    if (n_ranges) {
+        for (size_t q = 0; q < n_ranges; q++)
+            sub_ranges[(size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)ranges[q].stream) - cuts.begin()) - 1].push_back(q);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (hipSetDevice(ctx->device) != hipSuccess ||
+            (!ctx->check_stream && hipStreamCreateWithFlags(&ctx->check_stream, hipStreamNonBlocking) != hipSuccess))
+            return XLZ_ERR_DEVICE;
+    }
 
     std::vector<xlz_batch *> sub(S, nullptr);
     std::mutex mu;
@@ -2069,6 +2325,20 @@ extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, si
             t_decoded = now_ms();
         }
         cv.notify_all();
+        // (the downloader may go on: the check only reads the arena.  The digests are on the host when this returns,
+        //  long before the sub-batch is destroyed)
+        if (e == XLZ_OK && n_ranges && !sub_ranges[k].empty()) {
+            e = batch_checks_run(sub[k], ranges, sub_ranges[k].data(), sub_ranges[k].size(), cuts[k], digests, ctx->check_stream,
+                                 streams + cuts[k], chk);
+            if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu checked at %.1f ms\n", k, now_ms());
+            if (e != XLZ_OK) {
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    abort_all = true;
+                }
+                cv.notify_all();
+            }
+        }
         return e;
     };
     // true when sub-batch k's results are on the host (threaded: the launching thread collects them; else: do it here)
@@ -2211,7 +2481,45 @@ extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, si
     }
     ctx->pool.end_of_call();
     if (st == XLZ_OK && !big.empty()) st = decode_oversize(ctx, streams, results, big);
+    if (st == XLZ_OK && n_ranges) {
+        for (size_t q = 0; q < n_ranges && !big.empty(); q++) { // streams of 4 GiB and more: over the caller's buffer
+            const xlz_check_range &r = ranges[q];
+            if (!std::binary_search(big.begin(), big.end(), (size_t)r.stream)) continue;
+            const uint64_t produced = std::min<uint64_t>(results[r.stream].out_len, streams[r.stream].out_cap);
+            const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
+            digests[q] = hi > lo ? host_digest(r.kind, streams[r.stream].out + lo, hi - lo) : 0;
+            if (hi > lo)
+                chk.host_ranges++, chk.host_bytes += hi - lo;
+            else
+                chk.empty_ranges++;
+        }
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (accumulate) {
+            xlz_check_stats &t = ctx->last_check;
+            t.device_ranges += chk.device_ranges, t.device_bytes += chk.device_bytes, t.host_ranges += chk.host_ranges;
+            t.host_bytes += chk.host_bytes, t.empty_ranges += chk.empty_ranges, t.kernel_ms += chk.kernel_ms, t.launches += chk.launches;
+        } else {
+            ctx->last_check = chk;
+        }
+    }
     return st;
+}
+
+extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results)
+{
+    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, nullptr, false);
+}
+
+extern "C" int xlz_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                        const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests)
+{
+    return decode_batch_impl(ctx, streams, n, results, ranges, n_ranges, digests, false);
+}
+
+int xlz_internal_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                      const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, int accumulate)
+{
+    return decode_batch_impl(ctx, streams, n, results, ranges, n_ranges, digests, accumulate != 0);
 }
 
 // Multi-GPU form of xlz_decode_batch.  The streams are independent, and so are the units of an

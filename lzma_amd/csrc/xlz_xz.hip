@@ -20,6 +20,7 @@
 
 #include "../../include/xlz.h"
 #include "xlz_check.h"
+#include "xlz_check_host.h"
 
 namespace {
 
@@ -252,7 +253,29 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         d[i].format = XLZ_FMT_LZMA2_RAW;
         d[i].dict_size = blk[i].dict_size;
     }
-    st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), nb, r.data()) : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
+    // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 / CRC64 of every block comes from the device with the
+    // batch's results, dg[i] = block i's digest; the other check types stay with the host threads below
+    const bool dev = verify && n_ctx == 1 && xlz_ctx_check_mode(ctxs[0]) == 1;
+    std::vector<uint64_t> dg;
+    if (dev) {
+        std::vector<xlz_check_range> cr;
+        std::vector<uint64_t> got;
+        std::vector<size_t> of;
+        for (size_t i = 0; i < nb; i++)
+            if (blk[i].check_type == 1 || blk[i].check_type == 4) {
+                xlz_check_range c;
+                memset(&c, 0, sizeof c);
+                c.stream = i, c.off = 0, c.len = blk[i].uncomp_len, c.kind = blk[i].check_type;
+                cr.push_back(c);
+                of.push_back(i);
+            }
+        got.resize(cr.size());
+        dg.assign(nb, 0);
+        xlz_internal_check_stats_reset(ctxs[0]);
+        st = xlz_internal_decode_batch_checked(ctxs[0], d.data(), nb, r.data(), cr.data(), cr.size(), got.data(), 1);
+        for (size_t k = 0; k < of.size(); k++) dg[of[k]] = got[k];
+    } else
+        st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), nb, r.data()) : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
     if (st != XLZ_OK) return st;
     for (size_t i = 0; i < nb; i++) {
         if (r[i].status < 0) return r[i].status;
@@ -267,7 +290,9 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
             for (size_t i = t; i < nb; i += nth) {
                 const uint8_t *p = out + blk[i].uncomp_off;
                 const uint8_t *c = file + blk[i].check_off;
-                if (blk[i].check_type == 1)
+                if (dev && (blk[i].check_type == 1 || blk[i].check_type == 4))
+                    bad[i] = dg[i] != (blk[i].check_type == 1 ? (uint64_t)le32(c) : ((uint64_t)le32(c) | (uint64_t)le32(c + 4) << 32));
+                else if (blk[i].check_type == 1)
                     bad[i] = crc32(p, (size_t)blk[i].uncomp_len) != le32(c);
                 else if (blk[i].check_type == 4)
                     bad[i] = crc64(p, (size_t)blk[i].uncomp_len) != ((uint64_t)le32(c) | (uint64_t)le32(c + 4) << 32);
@@ -283,6 +308,9 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         for (unsigned t = 1; t < nth; t++) th.emplace_back(work, t);
         work(0);
         for (auto &x : th) x.join();
+        if (dev)
+            for (size_t i = 0; i < nb; i++)
+                if (blk[i].check_type == 10) xlz_internal_check_stats_host(ctxs[0], 1, blk[i].uncomp_len);
         size_t nu = 0;
         for (size_t i = 0; i < nb; i++) {
             if (bad[i] == 1) return XLZ_ERR_RESULT;

@@ -7,7 +7,8 @@ liblzma (Python's lzma module), hand-built .7z archives against their own plaint
        gpurun_out/lenient_xz_<seed>/, and anything but a payload case fails the run.
   .7z: a decode with verification on that succeeds has passed every CRC the archive carries: its bytes must be
        the original files'.
-usage: python tools/fuzz_containers.py [seconds] [seed]"""
+usage: python tools/fuzz_containers.py [seconds] [seed] [--alternate-check-mode]
+(--alternate-check-mode: every other round verifies CRC32 / CRC64 on the device, Context.set_check_mode(1))"""
 import lzma
 import os
 import random
@@ -112,7 +113,9 @@ def classify_lenient(b):
     return CONTAINER, "offset %d of %d: stream header / block header / index / footer / stream padding" % (off, len(b))
 
 
-def fuzz(ctx, seconds, seed, verbose=True):
+def fuzz(ctx, seconds, seed, verbose=True, alternate_check_mode=False):
+    """alternate_check_mode: every other round verifies on the device (Context.set_check_mode(1)): the outcome of a round
+    must not depend on it, the assertions are the same"""
     rnd = random.Random(seed)
     plains = [corpus.plain("TRMZ"[i % 4], 4000 + i, n) for i, n in enumerate((1, 300, 5000, 70000, 300000))]
     xzs = []
@@ -139,6 +142,8 @@ def fuzz(ctx, seconds, seed, verbose=True):
     save_dir = os.path.join(ROOT, "gpurun_out", "lenient_xz_%d" % seed)
     while time.time() < t_end:
         n += 1
+        if alternate_check_mode:
+            ctx.set_check_mode(n % 2)
         if rnd.random() < 0.6:
             b = bytes(_mutate(rnd, rnd.choice(xzs))) if rnd.random() < 0.85 else rnd.choice(xzs)
             ref = strict_xz(b)
@@ -188,6 +193,8 @@ def fuzz(ctx, seconds, seed, verbose=True):
             n_ok += 1
         if verbose and n % 200 == 0:
             print("%d inputs, %d decoded and equal, %d xz files liblzma refuses but xlz decodes" % (n, n_ok, n_lenient), flush=True)
+    if alternate_check_mode:
+        ctx.set_check_mode(0)
     if verbose:
         print("lenient .xz inputs by where liblzma refuses them: %r" % (buckets,), flush=True)
     return n, n_ok, n_lenient
@@ -196,4 +203,5 @@ def fuzz(ctx, seconds, seed, verbose=True):
 if __name__ == "__main__":
     secs = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    print("container fuzz ok: %d inputs, %d decoded and equal, %d lenient" % fuzz(lzma_amd.Context(0), secs, seed))
+    alt = "--alternate-check-mode" in sys.argv[3:]
+    print("container fuzz ok: %d inputs, %d decoded and equal, %d lenient" % fuzz(lzma_amd.Context(0), secs, seed, alternate_check_mode=alt))
