@@ -372,8 +372,10 @@ def test_random_crafted_lzma2_streams_gpu(ctx):
 
 
 @pytest.mark.gpu
-def test_crafted_streams_on_gpu(ctx):
+def test_crafted_streams_on_gpu(ctx, monkeypatch):
+    import kernel_streams
     import lzma_amd
+    kernel_streams.unforced(monkeypatch)
     from lzma_amd import FMT_LZMA2_RAW, FMT_LZMA_ALONE, Stream
     c1 = crafted_lzma1()
     got = lzma_amd.decode_batch(ctx, [Stream(b, FMT_LZMA_ALONE, out_cap=cap) for _, b, cap in c1])
@@ -389,6 +391,9 @@ def test_crafted_streams_on_gpu(ctx):
     c2.append(("off the headers into lc 8 / lp 4",) + walks_into_larger_props())
     c2.append(("off the headers into pb 4 (a compact-layout launch)",) + walks_into_larger_pb())
     streams = [Stream(b, FMT_LZMA2_RAW, out_cap=cap, dict_size=ds) for _, b, ds, cap in c2]
+    # (a crafted stream with a VISIBLE pb > 2 would turn this batch into a full-layout launch: the compact layout's stop
+    #  in front of pb 4 is what the last stream is here for -- tests/test_gpu_kernels.py has it on every compact kernel)
+    assert kernel_streams.kernel_of(ctx, streams + [extra])[0] == kernel_streams.KERNEL_NAMES["compact"]
     got = lzma_amd.decode_batch(ctx, streams + [extra])
     for (name, b, ds, cap), g in zip(c2, got):
         assert g == oracle.lzma2_raw(b, ds, cap), name

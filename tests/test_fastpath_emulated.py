@@ -55,6 +55,19 @@ def program():
     return _render()
 
 
+# the three loops the library ships: xlz_fastpath.inc, xlz_fastpath_pb2.inc, xlz_fastpath_pb2_br.inc (what launches of 24
+# workgroups per CU run: the headline kernel)
+COMMITTED_LOOPS = {"full": (), "compact": ("compact",), "branchy": ("compact", "dbr", "dbrs")}
+
+
+@pytest.fixture(scope="module", params=list(COMMITTED_LOOPS))
+def loop(request):
+    """each committed loop in turn: the tests of the loops' exits run on all three"""
+    prog = _render(COMMITTED_LOOPS[request.param])
+    assert (prog.lay["POS_STATES"] == 4) == (request.param != "full")
+    return prog
+
+
 def _head_vectors(lane, dpp=True, lay=None):
     """xlz_kernel.hip: head_vectors<L> (DPP cells; dpp=False: the XLZ_HEAD_PLAIN build, head probability j at lane j)"""
     P_LEN = lay["P_LEN"]
@@ -221,12 +234,7 @@ def test_generator_switches_still_decode(add, remove):
     assert (m.s["range"], m.s["code"], m.s["state"], m.s["rep0"]) == (rc.range, rc.code, st.state, st.reps[0])
 
 
-@pytest.mark.parametrize("without", [(), NEXT])
-def test_end_marker_and_error_exits(program, without):
-    """exit 2 (distance 0xFFFFFFFF: the end marker, decompress.go:633-645) on a stream of unknown size, and exit 1
-    (a distance the window does not hold, :651-653) on corrupted streams: same position and bytes as the oracle"""
-    if without:
-        program = _render((), without)   # round 2's loop
+def _end_marker_and_error_exits(program):
     lc, lp, pb, ds, n = 3, 0, 2, 1 << 16, 3000
     p = corpus.plain("T", 5, n)
     blob = corpus.compress_alone(p, dict_size=ds, known_size=False, preset=6)       # ends with the marker
@@ -251,13 +259,28 @@ def test_end_marker_and_error_exits(program, without):
     assert caught >= 2
 
 
-def test_every_load_is_waited_for_and_may_complete_as_late_as_its_wait(program):
+@pytest.mark.parametrize("without", [(), NEXT])
+def test_end_marker_and_error_exits(program, without):
+    """exit 2 (distance 0xFFFFFFFF: the end marker, decompress.go:633-645) on a stream of unknown size, and exit 1
+    (a distance the window does not hold, :651-653) on corrupted streams: same position and bytes as the oracle"""
+    if without:
+        program = _render((), without)   # round 2's loop
+    _end_marker_and_error_exits(program)
+
+
+def test_end_marker_and_error_exits_of_each_committed_loop(loop):
+    """the same on each of the three committed loops"""
+    _end_marker_and_error_exits(loop)
+
+
+def test_every_load_is_waited_for_and_may_complete_as_late_as_its_wait(loop):
     """the emulator's strict mode: the result of an LDS read or a global load is not in its register before the
     s_waitcnt that covers it (lgkmcnt / vmcnt counted as the hardware counts them, LDS in order), reading or
     overwriting it earlier is an error, and global loads read memory AT the wait -- the latest the hardware could.
     The committed loop decodes the same bytes as with loads that complete at issue: its s_waitcnt counts (the
     lgkmcnt(2) behind the literal walk's gather among them) are sufficient, and the deferred match copy does not
-    depend on when its load lands."""
+    depend on when its load lands.  On each of the three committed loops."""
+    program = loop
     for fam, n, lc, lp, pb, ds in (("T", 4000, 3, 0, 2, 1 << 16), ("M", 3000, 0, 2, 0, 4096)):
         p = corpus.plain(fam, 777 + n, n)
         blob = corpus.compress_alone(p, dict_size=ds, lc=lc, lp=lp, pb=pb, known_size=True, preset=6)
@@ -266,10 +289,12 @@ def test_every_load_is_waited_for_and_may_complete_as_late_as_its_wait(program):
         assert not m.pending and not m.vm                      # every exit has waited for what it started
 
 
-def test_dictionary_epoch_that_starts_inside_the_output(program):
+def test_dictionary_epoch_that_starts_inside_the_output(loop):
     """an LZMA2 unit behind a dictionary reset: positions are absolute in the output, the window starts at wbase
     (distance checks, the `window full` test and the copies' source test all use pos - wbase); 70 000 bytes in
-    front make the absolute positions differ from the window's in more than the low bits"""
+    front make the absolute positions differ from the window's in more than the low bits.  On each of the three
+    committed loops."""
+    program = loop
     lc, lp, pb, ds, n, base = 3, 0, 2, 4096, 7000, 70_000
     p = corpus.plain("M", 31, n)
     blob = corpus.compress_alone(p, dict_size=ds, known_size=True, preset=0)
@@ -286,7 +311,15 @@ def test_prepared_variants_on_a_window_that_wraps(program, without):
     configurations the switch test does not reach: a 4 KiB dictionary that wraps several times (nopos keeps the
     window's fill as max(window.pos, 0 or dictSize)) and an epoch that starts 70 000 bytes into the output, with
     late-landing loads"""
-    prog = _render((), without) if without else program
+    _prepared_variants_on_a_window_that_wraps(_render((), without) if without else program)
+
+
+def test_prepared_variants_on_a_window_that_wraps_in_each_committed_loop(loop):
+    """the same on each of the three committed loops (both rows have pb <= 2: the compact layout holds them)"""
+    _prepared_variants_on_a_window_that_wraps(loop)
+
+
+def _prepared_variants_on_a_window_that_wraps(prog):
     for fam, n, lc, lp, pb, ds, base in (("Z", 9000, 1, 1, 1, 4096, 0), ("M", 7000, 3, 0, 2, 4096, 70_000)):
         p = corpus.plain(fam, 4242 + n, n)
         blob = corpus.compress_alone(p, dict_size=ds, lc=lc, lp=lp, pb=pb, known_size=True, preset=0)
@@ -296,3 +329,16 @@ def test_prepared_variants_on_a_window_that_wraps(program, without):
         rc, st = _reference_state_at(blob[13:], lc, lp, pb, ds, n, len(out))
         assert (m.s["range"], m.s["code"], m.s["state"], m.s["prev"]) == (rc.range, rc.code, st.state, p[len(out) - 1])
         assert [m.s["rep0"], m.s["rep1"], m.s["rep2"], m.s["rep3"]] == st.reps
+
+
+def test_emulated_fuzz_of_each_committed_loop(loop):
+    """tools/fuzz_emulated.py in-process with a count and fixed seeds (a run is a function of its seed): random liblzma
+    streams -- families, sizes, lc / lp / pb (pb <= 2 on the compact layout), odd dictionary sizes that wrap, known and
+    unknown sizes, an output offset as behind a dictionary reset, headers that derail the decode into the error exit --
+    through each committed loop, half of them with strict waits.  A stream costs about two seconds."""
+    spec = importlib.util.spec_from_file_location("fuzz_emulated", os.path.join(ROOT, "tools", "fuzz_emulated.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    n_plain, b_plain = mod.fuzz(loop, seed=20260101, count=8, strict=False, verbose=False)
+    n_strict, b_strict = mod.fuzz(loop, seed=20260102, count=8, strict=True, verbose=False)
+    assert (n_plain, n_strict) == (8, 8) and b_plain > 0 and b_strict > 0

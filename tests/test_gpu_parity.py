@@ -6,6 +6,7 @@ import struct
 import pytest
 
 import corpus
+import kernel_streams
 import lzma_amd
 import oracle
 from lzma_amd import FMT_LZMA_ALONE, FMT_LZMA_RAW, Stream
@@ -80,45 +81,15 @@ def test_known_size_without_end_marker(ctx):
 
 
 def test_edge_cases_match_oracle(ctx):
-    p = corpus.plain("T", 5, 50_000)
-    c = corpus.compress_alone(p)
-    hdr = bytes([0x5D]) + struct.pack("<I", 65536) + struct.pack("<Q", 10)
-    blobs = [
-        b"",                                   # constructor: EOF
-        bytes([225]) + b"\0" * 20,             # ErrIncorrectProperties
-        bytes([0x5D, 0, 0]),                   # header cut
-        hdr,                                   # rangeDec.Init: EOF
-        hdr + b"\x01\0\0\0\0",                 # first rc byte != 0
-        hdr + b"\0\0\0",                       # rc init cut
-        c[: len(c) // 2],                      # truncated: clean EOF (parity note 4)
-        c[:20],
-        c[:14],
-        c,                                     # out_cap too small (below)
-        corpus.compress_alone(b""),            # empty plaintext, end marker only
-        corpus.compress_alone(b"", known_size=True),
-        corpus.compress_alone(b"x"),
-        c[:13] + bytes(len(c) - 13),           # all-zero payload
-        c[:13] + b"\0" + b"\xff" * 200,        # garbage payload
-        c[:5] + struct.pack("<Q", len(p) - 100) + c[13:],  # size too small: truncated match / error
-        c[:5] + struct.pack("<Q", len(p) + 100) + c[13:],  # size too large: marker with bytesLeft>0
-    ]
-    caps = [len(p)] * len(blobs)
-    caps[9] = 1000
+    blobs, caps = kernel_streams.lzma1_edge_blobs()
+    assert len(blobs) == 17
     _check_against_oracle(ctx, blobs, caps)
 
 
 def test_corrupted_streams_match_oracle(ctx):
-    import random
-    rnd = random.Random(42)
-    blobs = []
-    for i in range(48):
-        p = corpus.plain("TMZ"[i % 3], 200 + i, 40_000)
-        c = bytearray(corpus.compress_alone(p, known_size=(i % 4 == 0)))
-        for _ in range(rnd.randint(1, 3)):
-            k = rnd.randrange(13, len(c))
-            c[k] ^= 1 << rnd.randrange(8)
-        blobs.append(bytes(c))
-    _check_against_oracle(ctx, blobs, [41_000] * len(blobs))
+    blobs, caps = kernel_streams.lzma1_corrupted_blobs()
+    assert len(blobs) == 48
+    _check_against_oracle(ctx, blobs, caps)
 
 
 def test_sevenzip_style_raw_streams(ctx):
@@ -216,38 +187,15 @@ def test_lzma2_other_props_and_small_dict(ctx):
 
 
 def test_lzma2_framing_edge_cases_match_oracle(ctx):
-    p = corpus.plain("T", 620, 150_000)
-    c = corpus.lzma2_concat([p[:50_000], p[50_000:100_000], p[100_000:]], dict_size=1 << 16)
-    blobs = [
-        b"", b"\x00", b"\x03garbage", b"\x01\x00", b"\x01\x00\x02abc", b"\x01\x00\x02abc\x00", b"\x01\x00\x04ab",
-        b"\x02\x00\x02abc\x00",                       # stored, no dict reset as first chunk
-        b"\x80\x00\x00\x00\x04\x00\x00\x00\x00\x00\x00",  # LZMA chunk without props first
-        b"\xe0\x00\x00\x00\x04\xe1" + b"\0" * 5,      # bad props byte
-        b"\xe0\x00\x00\x00\x04\x5d\x01\0\0\0\0\x00",  # rc first byte != 0
-        b"\xe0\x00\x00\x00\x02\x5d\x00\0\0",          # rc init cut by the chunk limit
-        c[:-1],                                       # missing end byte -> ErrUnexpectedEOF
-        c[: len(c) // 2],                             # cut inside a chunk
-        c[: len(c) // 3] + c[len(c) // 3 + 5:],       # bytes dropped: headers no longer line up
-        c + b"trailing",                              # bytes after the end marker are ignored
-        c,                                            # out_cap too small (below)
-    ]
-    caps = [200_000] * len(blobs)
-    caps[-1] = 70_000
-    _check_lzma2(ctx, blobs, [1 << 16] * len(blobs), caps)
+    blobs, dicts, caps = kernel_streams.lzma2_framing_blobs()
+    assert len(blobs) == 17
+    _check_lzma2(ctx, blobs, dicts, caps)
 
 
 def test_lzma2_corrupted_streams_match_oracle(ctx):
-    import random
-    rnd = random.Random(7)
-    blobs = []
-    for i in range(40):
-        segs = [corpus.plain("TMZR"[(i + k) % 4], 700 + 10 * i + k, 15_000) for k in range(4)]
-        c = bytearray(corpus.lzma2_concat(segs, dict_size=1 << 16))
-        for _ in range(rnd.randint(1, 3)):
-            k = rnd.randrange(0, len(c))
-            c[k] ^= 1 << rnd.randrange(8)
-        blobs.append(bytes(c))
-    _check_lzma2(ctx, blobs, [1 << 16] * len(blobs), [80_000] * len(blobs))
+    blobs, dicts, caps = kernel_streams.lzma2_corrupted_blobs()
+    assert len(blobs) == 40
+    _check_lzma2(ctx, blobs, dicts, caps)
 
 
 # ------------------------------------------- pull-style readers (reader1.go / reader2.go) ----

@@ -3,7 +3,8 @@ dictionary sizes incl. odd ones that wrap, known / unknown size, an output offse
 reset) decoded by tools/gcn_emu.py running the loop -- the committed one or a set of generator switches -- and
 compared with the plaintext and, where the loop hands over, with the Python restatement's range / code / state /
 reps / prevByte / input position.  No GPU.
-usage: python tools/fuzz_emulated.py [seconds] [seed] [--variant a,b] [--without a,b] [--strict]"""
+usage: python tools/fuzz_emulated.py [seconds] [seed] [--count N] [--variant a,b] [--without a,b] [--strict]
+(--count N: stop after N streams instead of after a time)"""
 import os
 import random
 import sys
@@ -18,22 +19,21 @@ import oracle
 import test_fastpath_emulated as T
 
 
-def main():
-    a = sys.argv[1:]
-    add = a[a.index("--variant") + 1].split(",") if "--variant" in a else []
-    rem = a[a.index("--without") + 1].split(",") if "--without" in a else []
-    pos = [x for i, x in enumerate(a) if not x.startswith("--") and (i == 0 or a[i - 1] not in ("--variant", "--without"))]
-    secs = float(pos[0]) if pos else 60.0
-    rnd = random.Random(int(pos[1]) if len(pos) > 1 else 1)
-    prog = T._render(add, rem)
-    t_end = time.time() + secs
+def fuzz(prog, secs=None, seed=1, count=None, strict=False, dpp=True, verbose=True):
+    """random streams through `prog` (test_fastpath_emulated._render) until `count` streams have run, or for `secs`
+    seconds when no count is given: with a count, a run is a function of its seed.  A loop over the compact model layout
+    has room for four posStates: pb is drawn from 0..2 there.  -> (streams, bytes decoded by the emulated loop); raises
+    on a mismatch"""
+    rnd = random.Random(seed)
+    pb_max = 2 if "compact" in prog.variant else 4
+    t_end = time.time() + (secs if secs is not None else 60.0)
     n = nbytes = 0
-    while time.time() < t_end:
+    while (n < count) if count is not None else (time.time() < t_end):
         fam = rnd.choice("TRMZ")
         size = rnd.choice([400, 900, 2000, 3500, 6000])
         lc = rnd.randrange(0, 5)
         lp = rnd.randrange(0, 5 - lc)
-        pb = rnd.randrange(0, 5)
+        pb = rnd.randrange(0, pb_max + 1)
         ds = rnd.choice([4096, 4097, 5000, 6145, 8192, 65536])
         base = rnd.choice([0, 0, 0, 1, 4097, 70001])
         known = rnd.random() < 0.6
@@ -54,8 +54,7 @@ def main():
             # must stop where the real input ends: the kernel hands the last 32 bytes to the checked path)
             pad = b"\0" * 64 if (not known and status == 0 and want == p) else b""
             out, m, entries, exits, in_pos = T.run_fast_loop(prog, blob[13:] + pad, lc, lp, pb, ds, cap,
-                                                            junk + want + b"\0" * 8192, strict_waits="--strict" in a,
-                                                            dpp="hdpp" not in rem, base=base)
+                                                            junk + want + b"\0" * 8192, strict_waits=strict, dpp=dpp, base=base)
             assert out == want[:len(out)], "bytes differ"
             if exits[1]:
                 assert status == oracle.ERR_RESULT and out == want, "error exit where the oracle has none"
@@ -72,8 +71,20 @@ def main():
             raise
         n += 1
         nbytes += len(out)
-        if n % 20 == 0:
+        if verbose and n % 20 == 0:
             print("%d streams, %d bytes decoded by the emulated loop" % (n, nbytes), flush=True)
+    return n, nbytes
+
+
+def main():
+    a = sys.argv[1:]
+    valued = ("--variant", "--without", "--count")
+    add = a[a.index("--variant") + 1].split(",") if "--variant" in a else []
+    rem = a[a.index("--without") + 1].split(",") if "--without" in a else []
+    count = int(a[a.index("--count") + 1]) if "--count" in a else None
+    pos = [x for i, x in enumerate(a) if not x.startswith("--") and (i == 0 or a[i - 1] not in valued)]
+    n, nbytes = fuzz(T._render(add, rem), secs=float(pos[0]) if pos else 60.0, seed=int(pos[1]) if len(pos) > 1 else 1,
+                     count=count, strict="--strict" in a, dpp="hdpp" not in rem)
     print("emulated fuzz ok: %d streams, %d bytes" % (n, nbytes))
 
 
