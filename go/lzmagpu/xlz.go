@@ -717,6 +717,20 @@ func SetCheckMode(mode int) error {
 	return nil
 }
 
+// SetFilterMode says what DecodeXZ / Decode7z do with Delta / BCJ filter chains in front of an LZMA coder
+// (xlz_ctx_set_filter_mode): 0 refuse them (the default), 1 decode them and undo the filters on the GPU between decode and
+// check.
+func SetFilterMode(mode int) error {
+	c, err := context()
+	if err != nil {
+		return err
+	}
+	if st := C.xlz_ctx_set_filter_mode(c, C.int(mode)); st != C.XLZ_OK {
+		return ErrBadArgument
+	}
+	return nil
+}
+
 // CheckStats is xlz_check_stats: who checked what in the last checked call.
 type CheckStats struct {
 	DeviceRanges, DeviceBytes, HostRanges, HostBytes, EmptyRanges uint64
@@ -763,7 +777,12 @@ func DecodeXZ(file []byte, verify bool) ([]byte, error) {
 	fp, fl := cbuf(file)
 	var nBlocks C.size_t
 	var total C.uint64_t
-	if st := C.xlz_xz_index(fp, fl, nil, 0, &nBlocks, &total); st != C.XLZ_OK {
+	if C.xlz_ctx_filter_mode(c) == 1 { // (SetFilterMode: blocks may carry filter chains, which xlz_xz_index refuses)
+		var nSteps C.size_t
+		if st := C.xlz_xz_index_chains(fp, fl, nil, 0, &nBlocks, nil, 0, &nSteps, &total); st != C.XLZ_OK {
+			return nil, readError(st)
+		}
+	} else if st := C.xlz_xz_index(fp, fl, nil, 0, &nBlocks, &total); st != C.XLZ_OK {
 		return nil, readError(st)
 	}
 	out := make([]byte, int(total)+1)

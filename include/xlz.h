@@ -310,6 +310,61 @@ typedef struct xlz_check_stats {
 } xlz_check_stats;
 int xlz_ctx_last_check_stats(xlz_ctx *ctx, xlz_check_stats *out);
 
+/* ---- filters on the device ------------------------------------------------------------------
+ * Outside the reference (which has no filters).  The filters an .xz block or a .7z folder may put in front of its LZMA
+ * coder -- Delta and the BCJ branch converters -- undone by HIP kernels on the decoded bytes where they lie in HBM
+ * (lzma_amd/csrc/xlz_filter_dev.hip), before any check reads them and before they are downloaded.
+ * A STEP transforms [0, out_len) of one stream in place.  The steps of one stream are applied in array order to the decoded
+ * bytes -- the reverse of the order a block header lists its chain in --, at most three per stream; steps of different
+ * streams are independent: a launch takes one step of every stream that still has one.  ARM64 (0x0A), RISC-V (0x0B) and
+ * BCJ2 are not implemented.                                                                          */
+enum { XLZ_FILTER_DELTA = 3, XLZ_FILTER_X86 = 4, XLZ_FILTER_POWERPC = 5, XLZ_FILTER_IA64 = 6,
+       XLZ_FILTER_ARM = 7, XLZ_FILTER_ARMTHUMB = 8, XLZ_FILTER_SPARC = 9 };   /* the .xz filter ids */
+typedef struct xlz_filter_step {
+    uint64_t stream;   /* index into the call's / the batch's streams */
+    uint32_t id;       /* XLZ_FILTER_* */
+    uint32_t param;    /* Delta: distance 1..256; BCJ: start offset (a multiple of the filter's alignment) */
+    uint32_t reserved[2];
+} xlz_filter_step;
+/* XLZ_ERR_BAD_ARG (all entry points): an unknown id, a distance outside 1..256, a start offset that is not a multiple of
+ * the filter's alignment (x86 1, ARM-Thumb 2, ARM / PowerPC / SPARC 4, IA-64 16), non-zero reserved words, a stream index
+ * >= n, more than three steps for one stream.                                                         */
+/* One step over a host buffer: host only, no device needed (the serial form of what the kernels do).  What filters streams
+ * that never sit in an arena, and what a caller uses on bytes it decoded elsewhere.                   */
+int xlz_filter_host(uint32_t id, uint32_t param, uint8_t *buf, size_t len);
+/* Device-resident: waits for and collects the latest run like xlz_batch_checks and filters in place on the batch's stream.
+ * Afterwards xlz_batch_download, xlz_batch_device_output and xlz_batch_checks see the filtered bytes; a later
+ * xlz_batch_run decodes afresh.                                                                       */
+int xlz_batch_filter(xlz_batch *batch, const xlz_filter_step *steps, size_t n);
+/* xlz_decode_batch_checked with the filter between decode and check: digests are over the FILTERED bytes, which is what
+ * an .xz check and a .7z CRC cover.  With n_steps = 0 it is xlz_decode_batch_checked.  A (sub-)batch that has steps does
+ * not run sliced (xlz_call_stats.slices <= 1 for a call of one piece): a sliced call ships every slice's bytes while the
+ * next slice decodes, before a filter could see them; the pipelined forms hide piece k's filter and check under piece
+ * k + 1's decode as they are.  Streams of 4 GiB and more are filtered on the host over the caller's buffer
+ * (xlz_filter_stats.host_steps).  A stream with XLZ_STREAM_F_LZMA2_SLICE and a step: XLZ_ERR_BAD_ARG.  On a machine
+ * without a HIP device (no context can exist: ctx == NULL) the call returns XLZ_ERR_DEVICE: xlz_filter_host is no decoder. */
+int xlz_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                              const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                              uint64_t *digests);
+/* What xlz_xz_decode / xlz_7z_decode do with filter chains.  0 (default): they refuse them (XLZ_ERR_UNSUPPORTED), as ever.
+ * 1: they decode chains of one to three of the filters above in front of the LZMA coder.  The _multi forms ignore the
+ * mode.  Any other value: XLZ_ERR_BAD_ARG.                                                            */
+int xlz_ctx_set_filter_mode(xlz_ctx *ctx, int mode);
+int xlz_ctx_filter_mode(const xlz_ctx *ctx);
+/* Of the most recent xlz_batch_filter / xlz_decode_batch_filtered (with steps) on `ctx`, or of the most recent
+ * xlz_xz_decode / xlz_7z_decode in filter mode 1 (summed over the batches it made): what ran where.      */
+typedef struct xlz_filter_stats {
+    uint64_t device_steps; /* steps the kernels ran ...                                                  */
+    uint64_t device_bytes; /* ... and the bytes they covered (a stream of two steps counts twice)         */
+    uint64_t host_steps;   /* steps the host's code ran (streams outside the arenas)                      */
+    uint64_t host_bytes;
+    uint64_t empty_steps;  /* steps of streams that produced no byte                                      */
+    double kernel_ms;      /* the filter kernels by HIP events, summed over the (sub-)batches             */
+    uint32_t launches;     /* kernels queued (BCJ 1, x86 2, Delta 4 per round of steps)                   */
+    uint32_t reserved;
+} xlz_filter_stats;
+int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out);
+
 /* ---- pull-style readers mirroring the reference's Go surface --------------- */
 /* Constructors take the compressed stream as a buffer (a Go shim slurps its io.Reader
  * first) and copy it.  Constructor-time errors are the ones the reference's
@@ -429,8 +484,11 @@ int xlz_lzma2_units(const uint8_t *in, size_t len, xlz_lzma2_unit *units, size_t
 /* ---- .xz container front-end ----------------------------
  * Outside the reference (which has no container code): an .xz file is a list of independent
  * blocks, each ONE raw LZMA2 stream with its own dictionary -- what NewReader2(in, dictSize)
- * takes (reader2.go:26-41) -- so a file is one batch.  Only filter chains made of a single
- * LZMA2 filter are accepted (BCJ / delta: XLZ_ERR_UNSUPPORTED).                              */
+ * takes (reader2.go:26-41) -- so a file is one batch.  By default only filter chains made of a
+ * single LZMA2 filter are accepted (BCJ / Delta: XLZ_ERR_UNSUPPORTED); in filter mode 1
+ * (xlz_ctx_set_filter_mode) xlz_xz_decode also takes blocks with one to three Delta / BCJ filters
+ * in front of LZMA2 and undoes them on the device between decode and check (xlz_xz_index_chains
+ * lists them).  xlz_xz_index and xlz_xz_decode_multi refuse such blocks in either mode.         */
 typedef struct xlz_xz_block {
     uint64_t comp_off;   /* raw LZMA2 payload inside the file                                   */
     uint64_t comp_len;
@@ -446,6 +504,14 @@ typedef struct xlz_xz_block {
  * blocks than max_blocks (*n_blocks is the full count).                                      */
 int xlz_xz_index(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_blocks,
                  size_t *n_blocks, uint64_t *total_uncompressed);
+/* xlz_xz_index for files whose blocks carry filter chains: one to three of the filters Delta (0x03), x86 (0x04), PowerPC
+ * (0x05), IA-64 (0x06), ARM (0x07), ARM-Thumb (0x08), SPARC (0x09) in front of the LZMA2 filter.  Their steps come back
+ * in the order a decoder applies them (the reverse of the block header's), step.stream = the block's index; a block of
+ * one LZMA2 filter has none.  What liblzma refuses is XLZ_ERR_UNSUPPORTED: a wrong property size, a start offset that
+ * is not a multiple of the filter's alignment, LZMA2 not last, another filter last, ARM64 / RISC-V / unknown ids.
+ * steps may be NULL with max_steps 0 to obtain the count; XLZ_ERR_OUT_CAP: more steps than max_steps.      */
+int xlz_xz_index_chains(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_blocks, size_t *n_blocks,
+                        xlz_filter_step *steps, size_t max_steps, size_t *n_steps, uint64_t *total_uncompressed);
 /* Decode a whole .xz file into out as ONE GPU batch.  verify != 0: check every block's CRC32 /
  * CRC64 / SHA-256 on the host; *unverified (optional) = number of blocks whose check type is a
  * reserved one.  A failed check or a block that does not match the index:
@@ -467,8 +533,10 @@ int xlz_xz_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file,
  * (reader1.go:28-61 method 03 01 01, reader2.go:45-75 method 21).  A .7z archive keeps its data in
  * folders, each ONE compressed stream with out-of-band properties -- exactly what those
  * constructors take -- and folders are independent, so an archive is one batch.  Folders with a
- * single LZMA, LZMA2 or Copy coder are decoded; coder chains (BCJ + LZMA ...), encryption and
- * external / multi-volume layouts are reported as unsupported.  File names are not parsed: the
+ * single LZMA, LZMA2 or Copy coder are decoded; in filter mode 1 (xlz_ctx_set_filter_mode)
+ * xlz_7z_decode also takes folders that are a line of Delta / BCJ filters behind one LZMA / LZMA2
+ * coder (xlz_7z_index_chains) and undoes the filters on the device between decode and CRC.  Other
+ * coder graphs (BCJ2 ...), encryption and external / multi-volume layouts are reported as unsupported.  File names are not parsed: the
  * output is the folders' bytes back to back = the archive's files back to back.                */
 enum { XLZ_7Z_UNSUPPORTED = 0, XLZ_7Z_LZMA = 1, XLZ_7Z_LZMA2 = 2, XLZ_7Z_COPY = 3 };
 typedef struct xlz_7z_folder {
@@ -496,9 +564,19 @@ typedef struct xlz_7z_substream { /* one file's bytes inside a (solid) folder   
 int xlz_7z_index(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *folders,
                  size_t max_folders, size_t *n_folders, xlz_7z_substream *substreams,
                  size_t max_substreams, size_t *n_substreams, uint64_t *total_unpacked);
+/* xlz_7z_index for archives whose folders are coder chains.  A folder of 2-4 coders is accepted when every coder has one
+ * input and one output, the coders are bound into one line, there is exactly one packed stream, an LZMA / LZMA2 coder reads
+ * it and all the others are Delta (method 03, one property byte) or BCJ filters (x86 03030103, PowerPC 03030205, IA-64
+ * 03030401, ARM 03030501, ARM-Thumb 03030701, SPARC 03030805; no properties: start offset 0) and every size in the
+ * folder's unpack-size list is the same.  Such a folder carries the method, props and dictionary of its LZMA / LZMA2 coder,
+ * and its filters come back as steps in the order a decoder applies them, step.stream = the folder's index.  Anything
+ * else (BCJ2, encryption, ARM64, ...) stays XLZ_7Z_UNSUPPORTED.  xlz_7z_index keeps reporting every chain as method 0. */
+int xlz_7z_index_chains(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *folders, size_t max_folders,
+                        size_t *n_folders, xlz_7z_substream *substreams, size_t max_substreams, size_t *n_substreams,
+                        xlz_filter_step *steps, size_t max_steps, size_t *n_steps, uint64_t *total_unpacked);
 /* Decode every folder of a .7z archive into out as ONE GPU batch.  verify != 0: CRC32 of every file
  * (or folder) that carries one; *unverified (optional) = folders without any CRC.  XLZ_ERR_UNSUPPORTED
- * when a folder's coder chain is not a single LZMA / LZMA2 / Copy coder.                         */
+ * when a folder is not a single LZMA / LZMA2 / Copy coder (filter mode 1: nor a chain as above).   */
 int xlz_7z_decode(xlz_ctx *ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
                   uint64_t *out_len, int verify, size_t *unverified);
 /* the same over several contexts (one per GPU; encoded headers are decoded on the first)         */

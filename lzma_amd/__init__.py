@@ -15,6 +15,9 @@ from ._native import (EOF, ERR_BAD_ARG, ERR_CLOSED, ERR_DEVICE, ERR_HEADER_EOF, 
                       FMT_LZMA2_RAW, FMT_LZMA_ALONE, FMT_LZMA_RAW, NEED_INPUT, OK, OK_INPUT_EOF, UNKNOWN_SIZE,
                       CHECK_CRC32, CHECK_CRC64, CHECK_NONE)
 
+# the .xz filter ids (include/xlz.h: XLZ_FILTER_*)
+FILTER_DELTA, FILTER_X86, FILTER_POWERPC, FILTER_IA64, FILTER_ARM, FILTER_ARMTHUMB, FILTER_SPARC = 3, 4, 5, 6, 7, 8, 9
+
 
 class LzmaError(Exception):
     """A reference error value (errors.go:5-12 and friends) carried as a status code."""
@@ -119,6 +122,28 @@ class Context:
             raise LzmaError(st, "xlz_ctx_last_check_stats")
         return {k: getattr(cs, k) for k, _ in N.CheckStats._fields_ if k != "reserved"}
 
+    def set_filter_mode(self, mode):
+        """what xz_decode / sevenzip_decode do with Delta / BCJ filter chains (xlz_ctx_set_filter_mode): 0 refuse them
+        (default), 1 decode them and undo the filters on the device"""
+        st = N.lib().xlz_ctx_set_filter_mode(self._h, int(mode))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_set_filter_mode")
+
+    def filter_mode(self):
+        L = N.lib()
+        if not hasattr(L, "xlz_ctx_filter_mode"):  # (an older library loaded through XLZ_SO: it refuses every chain)
+            return 0
+        return L.xlz_ctx_filter_mode(self._h)
+
+    def last_filter_stats(self):
+        """what ran where in the last Batch.filter / decode_batch_filtered / front-end call in filter mode 1 on this context
+        (xlz_ctx_last_filter_stats) -> dict"""
+        fs = N.FilterStats()
+        st = N.lib().xlz_ctx_last_filter_stats(self._h, ctypes.byref(fs))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_filter_stats")
+        return {k: getattr(fs, k) for k, _ in N.FilterStats._fields_ if k != "reserved"}
+
     def event_record(self, slot):
         st = N.lib().xlz_ctx_event_record(self._h, slot)
         if st != OK:
@@ -204,6 +229,40 @@ def decode_batch_checked(ctx, streams, checks):
     st = N.lib().xlz_decode_batch_checked(ctx._h, descs, n, res, arr, len(checks), dig)
     if st != OK:
         raise LzmaError(st, "xlz_decode_batch_checked")
+    del keep
+    return [(outs[i].raw[: res[i].out_len], res[i].status, res[i].in_consumed) for i in range(n)], list(dig[: len(checks)])
+
+
+def _make_steps(steps):
+    """[(stream, filter id, parameter), ...] -> xlz_filter_step array"""
+    arr = (N.FilterStep * max(len(steps), 1))()
+    for q, (stream, fid, param) in enumerate(steps):
+        arr[q].stream, arr[q].id, arr[q].param = int(stream), int(fid), int(param)
+    return arr
+
+
+def filter_host(fid, param, data):
+    """one filter step (decoder side) over `data` on the host -> bytes (xlz_filter_host; no device needed).  fid: FILTER_*;
+    param: the Delta distance 1..256, or the BCJ start offset"""
+    buf = ctypes.create_string_buffer(bytes(data), len(data)) if len(data) else ctypes.create_string_buffer(1)
+    st = N.lib().xlz_filter_host(int(fid), int(param), ctypes.cast(buf, ctypes.c_void_p), len(data))
+    if st != OK:
+        raise LzmaError(st, "xlz_filter_host")
+    return buf.raw[: len(data)]
+
+
+def decode_batch_filtered(ctx, streams, steps, checks=()):
+    """decode_batch_checked with filter steps undone on the GPU between decode and check (xlz_decode_batch_filtered).
+    steps: [(stream index, FILTER_*, parameter), ...], the steps of one stream applied in list order; digests are over the
+    filtered bytes.  -> (list of (output bytes, status, in_consumed), list of digests)"""
+    streams, steps, checks = list(streams), list(steps), list(checks)
+    n = len(streams)
+    descs, keep, outs = _make_descs(streams)
+    res = (N.Result * max(n, 1))()
+    arr, dig = _make_ranges(checks)
+    st = N.lib().xlz_decode_batch_filtered(ctx._h, descs, n, res, _make_steps(steps), len(steps), arr, len(checks), dig)
+    if st != OK:
+        raise LzmaError(st, "xlz_decode_batch_filtered")
     del keep
     return [(outs[i].raw[: res[i].out_len], res[i].status, res[i].in_consumed) for i in range(n)], list(dig[: len(checks)])
 
@@ -360,6 +419,14 @@ class Batch:
         if st != OK:
             raise LzmaError(st, "xlz_batch_checks")
         return list(dig[: len(ranges)])
+
+    def filter(self, steps):
+        """undo filter steps in place on the decoded outputs, on the device (xlz_batch_filter): download, device_output and
+        checks see the filtered bytes afterwards.  steps: [(stream index, FILTER_*, parameter), ...]"""
+        steps = list(steps)
+        st = N.lib().xlz_batch_filter(self._h, _make_steps(steps), len(steps))
+        if st != OK:
+            raise LzmaError(st, "xlz_batch_filter")
 
     def download(self, i, length):
         buf = ctypes.create_string_buffer(max(int(length), 1))
@@ -618,10 +685,32 @@ def xz_index(data):
     return [{f: getattr(blocks[i], f) for f in fields} for i in range(n.value)], total.value
 
 
+def xz_index_chains(data):
+    """xz_index for files whose blocks carry Delta / BCJ filters in front of LZMA2 (xlz_xz_index_chains) -> (blocks, steps,
+    total): steps = [(block index, FILTER_*, parameter), ...] in the order a decoder applies them.  Host only."""
+    buf = ctypes.create_string_buffer(data, len(data)) if len(data) else ctypes.create_string_buffer(1)
+    n, ns = ctypes.c_size_t(), ctypes.c_size_t()
+    total = ctypes.c_uint64()
+    st = N.lib().xlz_xz_index_chains(ctypes.cast(buf, ctypes.c_void_p), len(data), None, 0, ctypes.byref(n), None, 0, ctypes.byref(ns),
+                                     ctypes.byref(total))
+    if st != OK:
+        raise LzmaError(st, "xlz_xz_index_chains")
+    blocks = (N.XzBlock * max(n.value, 1))()
+    steps = (N.FilterStep * max(ns.value, 1))()
+    st = N.lib().xlz_xz_index_chains(ctypes.cast(buf, ctypes.c_void_p), len(data), blocks, n.value, ctypes.byref(n), steps, ns.value,
+                                     ctypes.byref(ns), ctypes.byref(total))
+    if st != OK:
+        raise LzmaError(st, "xlz_xz_index_chains")
+    fields = [f for f, _ in N.XzBlock._fields_]
+    return ([{f: getattr(blocks[i], f) for f in fields} for i in range(n.value)],
+            [(steps[i].stream, steps[i].id, steps[i].param) for i in range(ns.value)], total.value)
+
+
 def xz_decode(ctx, data, verify=True, max_size=None):
     """Decode a whole .xz file (all streams, all blocks) as one GPU batch -> bytes.
-    verify: check every block's CRC32 / CRC64.  max_size: refuse (ERR_OUT_CAP) a file whose index announces more."""
-    _, total = xz_index(data)
+    verify: check every block's CRC32 / CRC64.  max_size: refuse (ERR_OUT_CAP) a file whose index announces more.
+    Blocks with Delta / BCJ filters are decoded when the context is in filter mode 1 (Context.set_filter_mode)."""
+    total = xz_index_chains(data)[2] if ctx.filter_mode() == 1 else xz_index(data)[1]
     if max_size is not None and total > max_size:
         raise LzmaError(ERR_OUT_CAP, "xlz_xz_decode: the index announces %d bytes, max_size is %d" % (total, max_size))
     out = ctypes.create_string_buffer(max(total, 1))
@@ -695,6 +784,30 @@ def sevenzip_index(data, ctx=None):
     fields = [f for f, _ in N.SzFolder._fields_ if f != "reserved"]
     return ([{f: getattr(fo[i], f) for f in fields} for i in range(nf.value)],
             [(su[i].size, su[i].crc if su[i].has_crc else None) for i in range(ns.value)], total.value)
+
+
+def sevenzip_index_chains(data, ctx=None):
+    """sevenzip_index for archives whose folders are Delta / BCJ filters behind an LZMA / LZMA2 coder (xlz_7z_index_chains)
+    -> (folders, files, steps, total): such a folder carries its LZMA / LZMA2 coder's method, props and dictionary, and
+    steps = [(folder index, FILTER_*, parameter), ...] in the order a decoder applies them"""
+    buf = ctypes.create_string_buffer(data, len(data)) if len(data) else ctypes.create_string_buffer(1)
+    h = ctx._h if ctx is not None else None
+    nf, ns, nst, total = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64()
+    st = N.lib().xlz_7z_index_chains(h, ctypes.cast(buf, ctypes.c_void_p), len(data), None, 0, ctypes.byref(nf), None, 0,
+                                     ctypes.byref(ns), None, 0, ctypes.byref(nst), ctypes.byref(total))
+    if st != OK:
+        raise LzmaError(st, "xlz_7z_index_chains")
+    fo = (N.SzFolder * max(nf.value, 1))()
+    su = (N.SzSubstream * max(ns.value, 1))()
+    steps = (N.FilterStep * max(nst.value, 1))()
+    st = N.lib().xlz_7z_index_chains(h, ctypes.cast(buf, ctypes.c_void_p), len(data), fo, nf.value, ctypes.byref(nf), su, ns.value,
+                                     ctypes.byref(ns), steps, nst.value, ctypes.byref(nst), ctypes.byref(total))
+    if st != OK:
+        raise LzmaError(st, "xlz_7z_index_chains")
+    fields = [f for f, _ in N.SzFolder._fields_ if f != "reserved"]
+    return ([{f: getattr(fo[i], f) for f in fields} for i in range(nf.value)],
+            [(su[i].size, su[i].crc if su[i].has_crc else None) for i in range(ns.value)],
+            [(steps[i].stream, steps[i].id, steps[i].param) for i in range(nst.value)], total.value)
 
 
 def sevenzip_decode(ctx, data, verify=True, max_size=None):

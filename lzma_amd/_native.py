@@ -52,6 +52,8 @@ EXPORTS = [
     "xlz_lzma2_units", "xlz_ctx_set_slicing", "xlz_ctx_trim", "xlz_batch_kernel_name", "xlz_decode_batch_plan",
     "xlz_batch_checks", "xlz_decode_batch_checked", "xlz_crc32_combine", "xlz_crc64_combine", "xlz_ctx_set_check_mode",
     "xlz_ctx_check_mode", "xlz_ctx_last_check_stats",
+    "xlz_filter_host", "xlz_batch_filter", "xlz_decode_batch_filtered", "xlz_ctx_set_filter_mode", "xlz_ctx_filter_mode",
+    "xlz_ctx_last_filter_stats", "xlz_xz_index_chains", "xlz_7z_index_chains",
 ]
 
 
@@ -94,6 +96,16 @@ class CheckRange(ctypes.Structure):
 class CheckStats(ctypes.Structure):
     _fields_ = [("device_ranges", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_ranges", ctypes.c_uint64),
                 ("host_bytes", ctypes.c_uint64), ("empty_ranges", ctypes.c_uint64), ("kernel_ms", ctypes.c_double),
+                ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class FilterStep(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint64), ("id", ctypes.c_uint32), ("param", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class FilterStats(ctypes.Structure):
+    _fields_ = [("device_steps", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_steps", ctypes.c_uint64),
+                ("host_bytes", ctypes.c_uint64), ("empty_steps", ctypes.c_uint64), ("kernel_ms", ctypes.c_double),
                 ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
@@ -265,6 +277,19 @@ def lib():
     L.xlz_xz_decode.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
     L.xlz_xz_decode_multi.argtypes = [ctypes.POINTER(vp), sz, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
     L.xlz_7z_decode_multi.argtypes = [ctypes.POINTER(vp), sz, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
+    if hasattr(L, "xlz_filter_host"):  # (an older library loaded through XLZ_SO for an A/B run has no filters)
+        L.xlz_filter_host.argtypes = [ctypes.c_uint32, ctypes.c_uint32, vp, sz]
+        L.xlz_batch_filter.argtypes = [vp, ctypes.POINTER(FilterStep), sz]
+        L.xlz_decode_batch_filtered.argtypes = [vp, ctypes.POINTER(StreamDesc), sz, ctypes.POINTER(Result), ctypes.POINTER(FilterStep), sz,
+                                                ctypes.POINTER(CheckRange), sz, ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_ctx_set_filter_mode.argtypes = [vp, i32]
+        L.xlz_ctx_filter_mode.argtypes = [vp]
+        L.xlz_ctx_last_filter_stats.argtypes = [vp, ctypes.POINTER(FilterStats)]
+        L.xlz_xz_index_chains.argtypes = [vp, sz, ctypes.POINTER(XzBlock), sz, ctypes.POINTER(sz), ctypes.POINTER(FilterStep), sz,
+                                          ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_7z_index_chains.argtypes = [vp, vp, sz, ctypes.POINTER(SzFolder), sz, ctypes.POINTER(sz), ctypes.POINTER(SzSubstream), sz,
+                                          ctypes.POINTER(sz), ctypes.POINTER(FilterStep), sz, ctypes.POINTER(sz),
+                                          ctypes.POINTER(ctypes.c_uint64)]
     _lib = L
     return L
 

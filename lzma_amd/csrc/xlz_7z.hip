@@ -118,7 +118,31 @@ struct Folder {
     bool has_crc = false;
     uint32_t crc = 0;
     uint64_t n_sub = 1;
+    // a LINE of 2-4 coders with one input and one output each, one packed stream, an LZMA / LZMA2 coder reading it and
+    // Delta / BCJ filters behind it (xlz_7z_index_chains, filter mode 1): the LZMA coder's method and properties, the
+    // filters in the order a decoder applies them
+    bool chain = false;
+    uint32_t chain_method = 0, chain_dict = 0;
+    uint8_t chain_props = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> steps; // (XLZ_FILTER_*, parameter)
 };
+
+// the filter a 7z method id names (7-Zip's Methods.txt), or 0
+uint32_t filter_of_method(const uint8_t *id, unsigned id_size)
+{
+    if (id_size == 1 && id[0] == 0x03) return XLZ_FILTER_DELTA;
+    if (id_size != 4 || id[0] != 0x03 || id[1] != 0x03) return 0;
+    const uint32_t m = (uint32_t)id[2] << 8 | id[3];
+    switch (m) {
+    case 0x0103: return XLZ_FILTER_X86;
+    case 0x0205: return XLZ_FILTER_POWERPC;
+    case 0x0401: return XLZ_FILTER_IA64;
+    case 0x0501: return XLZ_FILTER_ARM;
+    case 0x0701: return XLZ_FILTER_ARMTHUMB;
+    case 0x0805: return XLZ_FILTER_SPARC;
+    default: return 0;
+    }
+}
 
 struct Streams {
     uint64_t pack_pos = 0;
@@ -134,6 +158,13 @@ bool read_folder(Rd &r, Folder &f)
     if (n_coders == 0 || n_coders > 32) return false;
     uint64_t total_in = 0, total_out = 0;
     uint32_t method = XLZ_7Z_UNSUPPORTED;
+    struct Coder {
+        uint32_t kind = 0; // XLZ_7Z_LZMA / XLZ_7Z_LZMA2, 100: a filter, 0: anything else
+        uint32_t fid = 0, fparam = 0, dict = 0;
+        uint8_t props = 0;
+    };
+    std::vector<Coder> coders;
+    bool simple = n_coders >= 2 && n_coders <= 4; // every coder one input, one output
     for (uint64_t c = 0; c < n_coders; c++) {
         const uint8_t mb = r.byte();
         if (mb & 0xC0) return false; // reserved / alternative methods
@@ -157,6 +188,20 @@ bool read_folder(Rd &r, Folder &f)
         }
         total_in += n_in;
         total_out += n_out;
+        if (n_in != 1 || n_out != 1) simple = false;
+        if (simple) {
+            Coder cd;
+            const uint32_t fid = filter_of_method(id, id_size);
+            if (id_size == 3 && id[0] == 0x03 && id[1] == 0x01 && id[2] == 0x01 && psz == 5)
+                cd.kind = XLZ_7Z_LZMA, cd.props = r.p[ppos], cd.dict = le32(r.p + ppos + 1);
+            else if (id_size == 1 && id[0] == 0x21 && psz == 1)
+                cd.kind = XLZ_7Z_LZMA2, cd.props = r.p[ppos];
+            else if (fid == XLZ_FILTER_DELTA && psz == 1) // exactly one property byte (distance - 1), as 7-Zip demands
+                cd.kind = 100, cd.fid = fid, cd.fparam = (uint32_t)r.p[ppos] + 1;
+            else if (fid && fid != XLZ_FILTER_DELTA && psz == 0)
+                cd.kind = 100, cd.fid = fid;
+            coders.push_back(cd);
+        }
         if (n_coders == 1 && n_in == 1 && n_out == 1) {
             if (id_size == 3 && id[0] == 0x03 && id[1] == 0x01 && id[2] == 0x01 && psz == 5) { // LZMA, reader1.go:31
                 method = XLZ_7Z_LZMA;
@@ -173,9 +218,10 @@ bool read_folder(Rd &r, Folder &f)
     if (total_out == 0) return false;
     const uint64_t n_bind = total_out - 1;
     if (total_in < n_bind) return false;
+    std::vector<std::pair<uint64_t, uint64_t>> binds; // (input stream, the output stream that feeds it)
     for (uint64_t k = 0; k < n_bind; k++) {
-        r.number();
-        r.number();
+        const uint64_t in_index = r.number(), out_index = r.number();
+        if (simple) binds.emplace_back(in_index, out_index);
     }
     const uint64_t n_packed = total_in - n_bind;
     if (n_packed == 0) return false; // every folder consumes at least one packed stream
@@ -184,6 +230,34 @@ bool read_folder(Rd &r, Folder &f)
     f.method = method;
     f.n_pack = (uint32_t)n_packed;
     f.n_out = (uint32_t)total_out;
+    if (simple && n_packed == 1 && !r.bad) {
+        // with one stream in and out per coder, stream c is coder c's.  feeds[c] = the coder whose input coder c's output
+        // is, fed[c] = coder c's input comes from a coder; the line starts at the one coder that reads the packed stream
+        const size_t nc = coders.size();
+        std::vector<int> feeds(nc, -1), fed(nc, 0);
+        bool ok = true;
+        for (const auto &bp : binds) {
+            if (bp.first >= nc || bp.second >= nc || fed[(size_t)bp.first] || feeds[(size_t)bp.second] >= 0) ok = false;
+            if (!ok) break;
+            fed[(size_t)bp.first] = 1, feeds[(size_t)bp.second] = (int)bp.first;
+        }
+        size_t at = nc;
+        for (size_t c = 0; ok && c < nc; c++)
+            if (!fed[c]) at = c; // (exactly one: n_packed == 1)
+        ok = ok && at < nc && (coders[at].kind == XLZ_7Z_LZMA || coders[at].kind == XLZ_7Z_LZMA2);
+        if (ok) {
+            f.chain_method = coders[at].kind, f.chain_props = coders[at].props, f.chain_dict = coders[at].dict;
+            size_t seen = 1;
+            while (ok && feeds[at] >= 0) {
+                at = (size_t)feeds[at];
+                if (coders[at].kind != 100 || ++seen > nc) ok = false;
+                else f.steps.emplace_back(coders[at].fid, coders[at].fparam);
+            }
+            ok = ok && seen == nc;
+        }
+        if (!ok) f.steps.clear();
+        f.chain = ok;
+    }
     return !r.bad;
 }
 
@@ -219,11 +293,19 @@ int read_streams_info(Rd &r, Streams &s)
         for (auto &f : s.folders)
             if (!read_folder(r, f)) return XLZ_ERR_RESULT;
         if (r.byte() != kCodersUnPackSize) return XLZ_ERR_RESULT;
-        for (auto &f : s.folders)
+        for (auto &f : s.folders) {
+            uint64_t main_size = 0;
+            bool same = true;
             for (uint32_t k = 0; k < f.n_out; k++) {
                 const uint64_t v = r.number();
                 if (k + 1 == f.n_out || f.n_out == 1) f.unpack_size = v; // single coder: its one output
+                if (k == 0) main_size = v;
+                same = same && v == main_size;
             }
+            // a chain's filters keep the size: the folder's unpack size is that of the output no bind pair consumes, and
+            // every intermediate size must equal it
+            if (f.chain && !same) f.chain = false, f.steps.clear();
+        }
         id = r.byte();
         if (id == kCRC) {
             Digests d;
@@ -311,12 +393,15 @@ int read_streams_info(Rd &r, Streams &s)
 
 // lay the folders of a StreamsInfo out against the file: packed streams follow each other from
 // 32 + PackPos
-int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> &out)
+// chains: folders that are a chain (Folder::chain) are laid out as their LZMA / LZMA2 coder
+int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> &out, bool chains = false)
 {
     out.clear();
     uint64_t off = 32 + s.pack_pos, uoff = 0;
     size_t pi = 0, si = 0;
-    for (const Folder &f : s.folders) {
+    for (const Folder &f0 : s.folders) {
+        Folder f = f0;
+        if (chains && f.chain) f.method = f.chain_method, f.props = f.chain_props, f.dict_size = f.chain_dict;
         xlz_7z_folder o;
         memset(&o, 0, sizeof o);
         o.method = f.method;
@@ -351,8 +436,10 @@ int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> 
 // decode the given folders (all of a StreamsInfo) into `out`, verify their CRCs
 int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_folder> &fo,
                    const std::vector<xlz_7z_substream> &subs, uint8_t *out, int verify, size_t *unverified,
-                   xlz_ctx *const *ctxs = nullptr, size_t n_ctx = 0) // ctxs: deal the folders to several GPUs (xlz_decode_batch_multi)
+                   xlz_ctx *const *ctxs = nullptr, size_t n_ctx = 0, // ctxs: deal the folders to several GPUs (xlz_decode_batch_multi)
+                   const std::vector<Folder> *chains = nullptr)      // filter mode 1: the folders' filter steps (Folder::steps)
 {
+    std::vector<xlz_filter_step> fs;
     std::vector<xlz_stream_desc> d;
     std::vector<size_t> which;
     uint8_t propbuf[5];
@@ -380,6 +467,13 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
             s.format = XLZ_FMT_LZMA2_RAW;
             s.dict_size = f.dict_size;
         }
+        if (chains && (*chains)[i].chain)
+            for (const auto &stp : (*chains)[i].steps) {
+                xlz_filter_step q;
+                memset(&q, 0, sizeof q);
+                q.stream = d.size(), q.id = stp.first, q.param = stp.second;
+                fs.push_back(q);
+            }
         d.push_back(s);
         which.push_back(i);
     }
@@ -414,9 +508,14 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
         }
         dg.resize(cr.size());
         if (!d.empty()) {
-            int st = xlz_internal_decode_batch_checked(ctx, d.data(), d.size(), r.data(), cr.data(), cr.size(), dg.data(), 1);
+            int st = fs.empty() ? xlz_internal_decode_batch_checked(ctx, d.data(), d.size(), r.data(), cr.data(), cr.size(), dg.data(), 1)
+                                : xlz_internal_decode_batch_filtered(ctx, d.data(), d.size(), r.data(), fs.data(), fs.size(), cr.data(),
+                                                                     cr.size(), dg.data(), 1);
             if (st != XLZ_OK) return st;
         }
+    } else if (!fs.empty()) { // (CRCs, if asked for, on host threads below: over the filtered bytes)
+        int st = xlz_internal_decode_batch_filtered(ctx, d.data(), d.size(), r.data(), fs.data(), fs.size(), nullptr, 0, nullptr, 1);
+        if (st != XLZ_OK) return st;
     } else if (!d.empty()) {
         int st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), d.size(), r.data())
                            : xlz_decode_batch(ctx, d.data(), d.size(), r.data());
@@ -567,6 +666,48 @@ extern "C" int xlz_7z_index(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7
     return XLZ_OK;
 }
 
+// xlz_7z_index for archives whose folders are coder chains: a folder that is a line of Delta / BCJ filters behind one LZMA /
+// LZMA2 coder comes back with that coder's method, props and dictionary, and its filters as steps in the order a decoder
+// applies them, step.stream = the folder's index.
+extern "C" int xlz_7z_index_chains(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *folders, size_t max_folders,
+                                   size_t *n_folders, xlz_7z_substream *substreams, size_t max_substreams, size_t *n_substreams,
+                                   xlz_filter_step *steps, size_t max_steps, size_t *n_steps, uint64_t *total_unpacked)
+{
+    if (!file || !n_folders || !n_steps || (!folders && max_folders) || (!substreams && max_substreams) || (!steps && max_steps))
+        return XLZ_ERR_BAD_ARG;
+    *n_folders = 0, *n_steps = 0;
+    if (n_substreams) *n_substreams = 0;
+    if (total_unpacked) *total_unpacked = 0;
+    Streams s;
+    std::vector<uint8_t> dh;
+    int st = main_streams(ctx, file, len, s, dh);
+    if (st != XLZ_OK) return st;
+    std::vector<xlz_7z_folder> fo;
+    st = place_folders(s, len, fo, true);
+    if (st != XLZ_OK) return st;
+    uint64_t total = 0;
+    size_t ns = 0;
+    for (size_t i = 0; i < fo.size(); i++) {
+        if (i < max_folders) folders[i] = fo[i];
+        total += fo[i].unpack_len;
+        if (s.folders[i].chain)
+            for (const auto &stp : s.folders[i].steps) {
+                if (ns < max_steps) {
+                    memset(&steps[ns], 0, sizeof steps[ns]);
+                    steps[ns].stream = i, steps[ns].id = stp.first, steps[ns].param = stp.second;
+                }
+                ns++;
+            }
+    }
+    for (size_t i = 0; i < s.subs.size() && i < max_substreams; i++) substreams[i] = s.subs[i];
+    *n_folders = fo.size(), *n_steps = ns;
+    if (n_substreams) *n_substreams = s.subs.size();
+    if (total_unpacked) *total_unpacked = total;
+    if ((max_folders && fo.size() > max_folders) || (max_substreams && s.subs.size() > max_substreams) || (max_steps && ns > max_steps))
+        return XLZ_ERR_OUT_CAP;
+    return XLZ_OK;
+}
+
 static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
                      uint64_t *out_len, int verify, size_t *unverified);
 
@@ -599,13 +740,16 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     std::vector<uint8_t> dh;
     int st = main_streams(ctx, file, len, s, dh);
     if (st != XLZ_OK) return st;
+    // filter mode 1 (xlz_ctx_set_filter_mode; one context): folders that are a chain of filters behind an LZMA / LZMA2 coder
+    const bool chains = n_ctx == 1 && xlz_ctx_filter_mode(ctx) == 1;
+    if (chains) xlz_internal_filter_stats_reset(ctx);
     std::vector<xlz_7z_folder> fo;
-    st = place_folders(s, len, fo);
+    st = place_folders(s, len, fo, chains);
     if (st != XLZ_OK) return st;
     uint64_t total = 0;
     for (auto &f : fo) total += f.unpack_len;
     if (total > out_cap) return XLZ_ERR_OUT_CAP;
-    st = decode_folders(ctx, file, fo, s.subs, out, verify, unverified, ctxs, n_ctx);
+    st = decode_folders(ctx, file, fo, s.subs, out, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr);
     if (st != XLZ_OK) return st;
     *out_len = total;
     return XLZ_OK;

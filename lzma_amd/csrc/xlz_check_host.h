@@ -10,3 +10,8 @@ void xlz_internal_check_stats_host(xlz_ctx *ctx, uint64_t ranges, uint64_t bytes
 // xlz_decode_batch_checked; accumulate != 0: add to the context's statistics instead of starting them over
 int xlz_internal_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
                                       const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, int accumulate);
+// the same for filter mode 1: fresh statistics, and xlz_decode_batch_filtered with accumulate
+void xlz_internal_filter_stats_reset(xlz_ctx *ctx);
+int xlz_internal_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                       const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                                       uint64_t *digests, int accumulate);

@@ -30,6 +30,7 @@
 #include "xlz_check.h"
 #include "xlz_check_dev.h"
 #include "xlz_check_host.h"
+#include "xlz_filter_dev.h"
 
 using namespace xlz;
 
@@ -243,6 +244,9 @@ struct xlz_ctx {
     hipStream_t check_stream = nullptr;
     int check_mode = 0;
     xlz_check_stats last_check = {}; // xlz_ctx_last_check_stats
+    // filters (xlz_filter_dev.hip): xlz_ctx_set_filter_mode, xlz_ctx_last_filter_stats
+    int filter_mode = 0;
+    xlz_filter_stats last_filter = {};
 };
 
 // per-stream bookkeeping of a batch
@@ -325,6 +329,11 @@ struct xlz_batch {
     uint8_t *d_chk = nullptr, *pin_chk = nullptr;
     size_t d_chk_cap = 0, pin_chk_cap = 0;
     hipEvent_t chk_ev0 = nullptr, chk_ev1 = nullptr;
+    // xlz_batch_filter / xlz_decode_batch_filtered: step tables | window table | rows of sums on the device, the step tables
+    // in pinned memory (grow-only, kept until the batch goes), and the events around the filter kernels
+    uint8_t *d_flt = nullptr, *pin_flt = nullptr;
+    size_t d_flt_cap = 0, pin_flt_cap = 0;
+    hipEvent_t flt_ev0 = nullptr, flt_ev1 = nullptr;
 };
 
 // ---------------------------------------------------------------- helpers ----
@@ -808,6 +817,10 @@ int batch_free(xlz_batch *b)
     batch_release(b, b->pin_chk, true);
     if (b->chk_ev0) (void)hipEventDestroy(b->chk_ev0);
     if (b->chk_ev1) (void)hipEventDestroy(b->chk_ev1);
+    batch_release(b, b->d_flt);
+    batch_release(b, b->pin_flt, true);
+    if (b->flt_ev0) (void)hipEventDestroy(b->flt_ev0);
+    if (b->flt_ev1) (void)hipEventDestroy(b->flt_ev1);
     delete b;
     return XLZ_OK;
 }
@@ -1833,6 +1846,195 @@ void xlz_internal_check_stats_host(xlz_ctx *ctx, uint64_t ranges, uint64_t bytes
     ctx->last_check.host_ranges += ranges, ctx->last_check.host_bytes += bytes;
 }
 
+// ---------------------------------------------------------------- filters on the device ----
+namespace xlz {
+int filter_launch(int cls, uint8_t *arena, const xlzflt::DevStep *steps, uint32_t n_steps, uint32_t total_tiles, void *scratch,
+                  void *scratch2, uint32_t total_groups, hipStream_t stream);
+}
+
+namespace {
+
+constexpr size_t kMaxStepsPerStream = 3;
+
+// per stream of [base, base + count): the indices of its steps, in array order; XLZ_ERR_BAD_ARG for a step the library
+// does not run, a stream outside the call or more than three steps for one stream
+int filter_args(const xlz_filter_step *steps, size_t n_steps, size_t n_streams)
+{
+    if (!steps && n_steps) return XLZ_ERR_BAD_ARG;
+    std::vector<uint8_t> count;
+    for (size_t q = 0; q < n_steps; q++) {
+        const xlz_filter_step &f = steps[q];
+        if (f.stream >= n_streams || f.reserved[0] || f.reserved[1] || xlzflt::bad_step(f.id, f.param)) return XLZ_ERR_BAD_ARG;
+        if (count.empty()) count.assign(n_streams, 0);
+        if (++count[(size_t)f.stream] > kMaxStepsPerStream) return XLZ_ERR_BAD_ARG;
+    }
+    return XLZ_OK;
+}
+
+void filter_stats_add(xlz_filter_stats &t, const xlz_filter_stats &a)
+{
+    t.device_steps += a.device_steps, t.device_bytes += a.device_bytes, t.host_steps += a.host_steps, t.host_bytes += a.host_bytes;
+    t.empty_steps += a.empty_steps, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
+}
+
+// Applies steps[idx[0 .. n_idx)] (idx == nullptr: steps[0 .. n_idx)) to the streams of a COLLECTED batch whose stream
+// `stream_base` is the batch's first, in place in the output arena: collect() has waited for everything that writes the
+// arena, its re-runs included.  Round r of launches takes the r-th step of every stream that has one; all rounds are
+// queued on `stream` and waited for.  Streams outside the arena are skipped: they have no bytes (settled while parsing)
+// or are filtered on the host behind the call (oversize).
+int batch_filter_run(xlz_batch *b, const xlz_filter_step *steps, const size_t *idx, size_t n_idx, size_t stream_base, hipStream_t stream,
+                     xlz_filter_stats &acc)
+{
+    using xlzflt::DevStep;
+    if (!n_idx) return XLZ_OK;
+    struct Round {
+        std::vector<DevStep> tab[3]; // fixed-width BCJ, x86, Delta
+        uint64_t tiles[3] = {0, 0, 0}, windows = 0, rows = 0, groups = 0;
+    };
+    Round rounds[kMaxStepsPerStream];
+    std::vector<uint8_t> depth(b->n, 0);
+    uint64_t dev_bytes = 0, dev_steps = 0;
+    for (size_t q = 0; q < n_idx; q++) {
+        const xlz_filter_step &f = steps[idx ? idx[q] : q];
+        const size_t s = (size_t)(f.stream - stream_base);
+        const StreamPlan &pl = b->plans[s];
+        if (pl.oversize) continue;
+        const uint64_t produced = pl.host_status == 1 ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : 0;
+        if (!produced) {
+            acc.empty_steps++;
+            continue;
+        }
+        if (depth[s] >= kMaxStepsPerStream || pl.out_off + produced > b->out_bytes || (pl.out_off & 15)) return XLZ_ERR_UNSUPPORTED;
+        Round &R = rounds[depth[s]++];
+        const int cls = f.id == XLZ_FILTER_X86 ? 1 : f.id == XLZ_FILTER_DELTA ? 2 : 0;
+        DevStep d;
+        d.off = pl.out_off, d.len = produced, d.id = f.id, d.param = f.param, d.aux = 0, d.aux2 = 0;
+        uint64_t tiles;
+        if (cls == 0) {
+            tiles = (produced + xlzflt::kBcjTileBytes - 1) / xlzflt::kBcjTileBytes;
+        } else if (cls == 1) {
+            const uint64_t w = xlzflt::x86_windows(produced);
+            tiles = (w + xlzflt::kX86TileWindows - 1) / xlzflt::kX86TileWindows;
+            d.aux = R.windows, R.windows += w;
+        } else {
+            tiles = xlzflt::delta_chunks(produced);
+            d.aux = R.rows, R.rows += tiles;
+            d.aux2 = R.groups, R.groups += xlzflt::delta_groups(tiles);
+        }
+        if (R.tiles[cls] + tiles > 0x7FFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+        d.first = (uint32_t)R.tiles[cls], d.n_tiles = (uint32_t)tiles;
+        R.tiles[cls] += tiles;
+        R.tab[cls].push_back(d);
+        dev_bytes += produced, dev_steps++;
+    }
+    if (!dev_steps) return XLZ_OK;
+    size_t tab_bytes = 0, scratch_bytes = 0;
+    for (const Round &R : rounds) {
+        for (int c = 0; c < 3; c++) tab_bytes += R.tab[c].size() * sizeof(DevStep);
+        scratch_bytes = std::max<size_t>(scratch_bytes, align_up((size_t)R.windows * 2, 256) + (size_t)(R.rows + R.groups) * xlzflt::kDeltaMaxDist);
+    }
+    xlz_ctx *ctx = b->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t tab_room = align_up(tab_bytes, 256);
+    if (b->d_flt_cap < tab_room + scratch_bytes) {
+        batch_release(b, b->d_flt);
+        b->d_flt = nullptr, b->d_flt_cap = 0;
+        if (!batch_alloc(b, &b->d_flt, tab_room + scratch_bytes)) return XLZ_ERR_DEVICE;
+        b->d_flt_cap = tab_room + scratch_bytes;
+    }
+    if (b->pin_flt_cap < tab_bytes) {
+        batch_release(b, b->pin_flt, true);
+        b->pin_flt = nullptr, b->pin_flt_cap = 0;
+        if (!batch_alloc(b, &b->pin_flt, tab_bytes, true)) return XLZ_ERR_DEVICE;
+        b->pin_flt_cap = tab_bytes;
+    }
+    if (!b->flt_ev0) HIP_TRY(hipEventCreate(&b->flt_ev0));
+    if (!b->flt_ev1) HIP_TRY(hipEventCreate(&b->flt_ev1));
+    size_t at = 0;
+    for (const Round &R : rounds)
+        for (int c = 0; c < 3; c++)
+            if (!R.tab[c].empty()) {
+                memcpy(b->pin_flt + at, R.tab[c].data(), R.tab[c].size() * sizeof(DevStep));
+                at += R.tab[c].size() * sizeof(DevStep);
+            }
+    HIP_TRY(hipMemcpyAsync(b->d_flt, b->pin_flt, tab_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(b->flt_ev0, stream));
+    uint8_t *d_scratch = b->d_flt + tab_room;
+    uint32_t launches = 0;
+    at = 0;
+    for (const Round &R : rounds) {
+        uint8_t *d_rows = d_scratch + align_up((size_t)R.windows * 2, 256);
+        for (int c = 0; c < 3; c++) {
+            if (R.tab[c].empty()) continue;
+            const int k = xlz::filter_launch(c, b->d_out, reinterpret_cast<const DevStep *>(b->d_flt + at), (uint32_t)R.tab[c].size(),
+                                             (uint32_t)R.tiles[c], c == 2 ? d_rows : d_scratch, d_rows + (size_t)R.rows * xlzflt::kDeltaMaxDist,
+                                             (uint32_t)R.groups, stream);
+            if (k < 0) {
+                if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the filter kernels failed\n");
+                (void)hipStreamSynchronize(stream);
+                return XLZ_ERR_DEVICE;
+            }
+            launches += (uint32_t)k;
+            at += R.tab[c].size() * sizeof(DevStep);
+        }
+    }
+    HIP_TRY(hipEventRecord(b->flt_ev1, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, b->flt_ev0, b->flt_ev1));
+    acc.device_steps += dev_steps, acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches += launches;
+    return XLZ_OK;
+}
+
+} // namespace
+
+extern "C" int xlz_filter_host(uint32_t id, uint32_t param, uint8_t *buf, size_t len)
+{
+    if ((!buf && len) || xlzflt::bad_step(id, param)) return XLZ_ERR_BAD_ARG;
+    xlzflt::host_apply(id, param, buf, len);
+    return XLZ_OK;
+}
+
+extern "C" int xlz_batch_filter(xlz_batch *b, const xlz_filter_step *steps, size_t n)
+{
+    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
+    int st = filter_args(steps, n, b->n);
+    if (st != XLZ_OK) return st;
+    st = collect(b);
+    if (st != XLZ_OK) return st;
+    xlz_filter_stats acc;
+    memset(&acc, 0, sizeof acc);
+    st = batch_filter_run(b, steps, nullptr, n, 0, b->run_stream ? b->run_stream : b->ctx->stream, acc);
+    if (st != XLZ_OK) return st;
+    std::lock_guard<std::mutex> lock(b->ctx->mu);
+    b->ctx->last_filter = acc;
+    return XLZ_OK;
+}
+
+extern "C" int xlz_ctx_set_filter_mode(xlz_ctx *ctx, int mode)
+{
+    if (!ctx || (mode != 0 && mode != 1)) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->filter_mode = mode;
+    return XLZ_OK;
+}
+extern "C" int xlz_ctx_filter_mode(const xlz_ctx *ctx) { return ctx ? ctx->filter_mode : XLZ_ERR_BAD_ARG; }
+
+extern "C" int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out)
+{
+    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *out = ctx->last_filter;
+    return XLZ_OK;
+}
+
+void xlz_internal_filter_stats_reset(xlz_ctx *ctx)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    memset(&ctx->last_filter, 0, sizeof ctx->last_filter);
+}
+
 namespace {
 
 // Moves n chunks from the device to the callers' buffers through the context's pinned ring (one download at a time per
@@ -2210,15 +2412,21 @@ extern "C" int xlz_decode_batch_plan(const xlz_stream_desc *streams, size_t n, s
     return max_cuts && c.size() > max_cuts ? XLZ_ERR_OUT_CAP : XLZ_OK;
 }
 
-// xlz_decode_batch (n_ranges == 0) and xlz_decode_batch_checked: the digests of `ranges` are computed on the device behind
-// the results of every (sub-)batch, while its arenas are still the call's
-static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const xlz_check_range *ranges,
-                             size_t n_ranges, uint64_t *digests, bool accumulate)
+// xlz_decode_batch (n_steps == 0, n_ranges == 0), xlz_decode_batch_checked (n_steps == 0) and xlz_decode_batch_filtered:
+// the filter steps of every (sub-)batch run on the device behind its results and BEFORE it is published as decoded (the
+// downloader starts then, and the filters write); the digests of `ranges` are computed behind them, while the arenas are
+// still the call's.  A sub-batch that has steps never runs sliced: a sliced call ships every slice's bytes while the next
+// slice decodes, before any filter could see them (per-slice filtering with carried state is later work).
+static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const xlz_filter_step *steps,
+                             size_t n_steps, const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, bool accumulate)
 {
     if (!ctx || (!streams && n) || (!results && n)) return XLZ_ERR_BAD_ARG;
     for (size_t i = 0; i < n; i++)
         if (!streams[i].out && streams[i].out_cap) return XLZ_ERR_BAD_ARG;
     if (check_args(ranges, n_ranges, n, digests) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    if (filter_args(steps, n_steps, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    for (size_t q = 0; q < n_steps; q++)
+        if (streams[steps[q].stream].flags & XLZ_STREAM_F_LZMA2_SLICE) return XLZ_ERR_BAD_ARG; // (a filter needs the stream's start)
     // upload (pinned image, one copy) -> decode -> download (pinned ring, D2H overlapped with the scatter into the
     // callers' buffers).  A call of several wave rounds runs as a PIPELINE of sub-batches on three host threads:
     // sub-batch k+1 is parsed, packed and uploaded and sub-batch k-1 is downloaded and scattered while sub-batch k
@@ -2245,10 +2453,17 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
         std::lock_guard<std::mutex> lock(ctx->mu); // (once: the launching thread holds this lock most of the call)
         sliced_call_bytes = ctx->sliced_call_bytes, slice_bytes = ctx->slice_bytes, max_slices = ctx->max_slices;
     }
+    // filtered calls: the steps of every sub-batch (in array order)
+    std::vector<std::vector<size_t>> sub_steps(n_steps ? S : 0);
+    for (size_t q = 0; q < n_steps; q++)
+        sub_steps[(size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)steps[q].stream) - cuts.begin()) - 1].push_back(q);
+    xlz_filter_stats flt;
+    memset(&flt, 0, sizeof flt);
     auto slices_for = [&](size_t k) -> uint32_t {
         // (in a pipeline the pieces overlap each other; slices of the first or last piece were measured there: the next
         //  piece's workgroups take the slots every slice boundary frees and the two pieces finish together)
         if (S > 1 && !rounds_mode) return 1;
+        if (n_steps && !sub_steps[k].empty()) return 1; // (a filter must see the bytes before they leave: see above)
         uint64_t total = 0;
         for (size_t i = cuts[k]; i < cuts[k + 1]; i++) total += streams[i].out_cap;
         return total >= sliced_call_bytes ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_slices, total / slice_bytes)) : 1u;
@@ -2260,7 +2475,7 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
     std::vector<std::vector<size_t>> sub_ranges(n_ranges ? S : 0);
     xlz_check_stats chk;
     memset(&chk, 0, sizeof chk);
-    if (n_ranges) {
+    if (n_ranges || n_steps) {
         for (size_t q = 0; q < n_ranges; q++)
             sub_ranges[(size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)ranges[q].stream) - cuts.begin()) - 1].push_back(q);
         std::lock_guard<std::mutex> lock(ctx->mu);
@@ -2318,6 +2533,12 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
                 for (const UnitResult &u : sub[k]->unit_results) clock.add(u);
         }
         if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu decoded at %.1f ms\n", k, now_ms());
+        // (xlz_batch_results has run collect() and its re-runs, which write bytes again; nobody reads the arena yet.  On the
+        //  check stream for the reason given above; the checks follow on the same stream)
+        if (e == XLZ_OK && n_steps && !sub_steps[k].empty()) {
+            e = batch_filter_run(sub[k], steps, sub_steps[k].data(), sub_steps[k].size(), cuts[k], ctx->check_stream, flt);
+            if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu filtered at %.1f ms\n", k, now_ms());
+        }
         {
             std::lock_guard<std::mutex> lk(mu);
             decoded[k] = e == XLZ_OK ? 1 : -1;
@@ -2481,6 +2702,22 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
     }
     ctx->pool.end_of_call();
     if (st == XLZ_OK && !big.empty()) st = decode_oversize(ctx, streams, results, big);
+    if (st == XLZ_OK && n_steps) {
+        for (size_t q = 0; q < n_steps && !big.empty(); q++) { // streams of 4 GiB and more: over the caller's buffer, in array order
+            const xlz_filter_step &f = steps[q];
+            if (!std::binary_search(big.begin(), big.end(), (size_t)f.stream)) continue;
+            const uint64_t produced = std::min<uint64_t>(results[f.stream].out_len, streams[f.stream].out_cap);
+            if (produced)
+                xlzflt::host_apply(f.id, f.param, streams[f.stream].out, produced), flt.host_steps++, flt.host_bytes += produced;
+            else
+                flt.empty_steps++;
+        }
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (accumulate)
+            filter_stats_add(ctx->last_filter, flt);
+        else
+            ctx->last_filter = flt;
+    }
     if (st == XLZ_OK && n_ranges) {
         for (size_t q = 0; q < n_ranges && !big.empty(); q++) { // streams of 4 GiB and more: over the caller's buffer
             const xlz_check_range &r = ranges[q];
@@ -2507,19 +2744,35 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
 
 extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results)
 {
-    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, nullptr, false);
+    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, nullptr, 0, nullptr, false);
 }
 
 extern "C" int xlz_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
                                         const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests)
 {
-    return decode_batch_impl(ctx, streams, n, results, ranges, n_ranges, digests, false);
+    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, ranges, n_ranges, digests, false);
+}
+
+extern "C" int xlz_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                         const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                                         uint64_t *digests)
+{
+    // (a machine without a HIP device has no context to pass; the filters of such a call are not run on the host instead)
+    if (!ctx && xlz_device_count() == 0) return XLZ_ERR_DEVICE;
+    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, digests, false);
+}
+
+int xlz_internal_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                       const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                                       uint64_t *digests, int accumulate)
+{
+    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, digests, accumulate != 0);
 }
 
 int xlz_internal_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
                                       const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, int accumulate)
 {
-    return decode_batch_impl(ctx, streams, n, results, ranges, n_ranges, digests, accumulate != 0);
+    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, ranges, n_ranges, digests, accumulate != 0);
 }
 
 // Multi-GPU form of xlz_decode_batch.  The streams are independent, and so are the units of an

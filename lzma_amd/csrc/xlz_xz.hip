@@ -9,8 +9,9 @@
 //
 // Host-only code (no kernels here).  Format: "The .xz File Format" 1.0.4 (tukaani.org), restated
 // from the published specification; nothing of it exists in the reference.  Only what feeds the
-// LZMA2 path is implemented: filter chains with anything but a single LZMA2 filter (BCJ, delta)
-// are reported as XLZ_ERR_UNSUPPORTED.
+// LZMA2 path is implemented: a block is one LZMA2 filter, or -- xlz_xz_index_chains, and xlz_xz_decode in
+// filter mode 1 -- one to three Delta / BCJ filters in front of it, which become filter steps of the
+// batch (xlz_filter_dev.hip).  ARM64, RISC-V and every other filter id: XLZ_ERR_UNSUPPORTED.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "../../include/xlz.h"
 #include "xlz_check.h"
 #include "xlz_check_host.h"
+#include "xlz_filter_dev.h"
 
 namespace {
 
@@ -109,9 +111,12 @@ int parse_stream_backwards(const uint8_t *f, size_t end, Stream &s)
     return XLZ_OK;
 }
 
-// block header (spec 3.1): only "one LZMA2 filter" chains are accepted
+// block header (spec 3.1).  chain == nullptr: only "one LZMA2 filter" chains are accepted.  Otherwise up to three Delta /
+// BCJ filters may precede the LZMA2 filter; they are returned in the order the header lists them (the encoder's: the
+// decoder undoes them last to first).  What liblzma refuses is refused: a property size that is not the filter's, a start
+// offset that is not a multiple of the filter's alignment, LZMA2 anywhere but last, anything else last.
 int parse_block_header(const uint8_t *p, size_t avail, size_t &hdr_size, uint32_t &dict, uint64_t &comp_size,
-                       uint64_t &uncomp_size)
+                       uint64_t &uncomp_size, std::vector<std::pair<uint32_t, uint32_t>> *chain = nullptr)
 {
     if (avail < 8 || p[0] == 0) return XLZ_ERR_RESULT;
     hdr_size = ((size_t)p[0] + 1) * 4;
@@ -132,6 +137,12 @@ int parse_block_header(const uint8_t *p, size_t avail, size_t &hdr_size, uint32_
         if (id == 0x21 && psz == 1 && k + 1 == nfilters) {
             if (!xz_dict_size(p[pos], dict)) return XLZ_ERR_RESULT;
             have_lzma2 = true;
+        } else if (chain && k + 1 < nfilters && id == XLZ_FILTER_DELTA && psz == 1) {
+            chain->emplace_back((uint32_t)id, (uint32_t)p[pos] + 1);
+        } else if (chain && k + 1 < nfilters && id >= XLZ_FILTER_X86 && id <= XLZ_FILTER_SPARC && (psz == 0 || psz == 4)) {
+            const uint32_t start = psz ? le32(p + pos) : 0;
+            if (xlzflt::bad_step((uint32_t)id, start)) return XLZ_ERR_UNSUPPORTED;
+            chain->emplace_back((uint32_t)id, start);
         } else {
             return XLZ_ERR_UNSUPPORTED; // BCJ / delta / anything else in the chain
         }
@@ -139,8 +150,11 @@ int parse_block_header(const uint8_t *p, size_t avail, size_t &hdr_size, uint32_
     }
     while (pos < hdr_size - 4)
         if (p[pos++] != 0) return XLZ_ERR_RESULT;
-    return have_lzma2 && nfilters == 1 ? XLZ_OK : XLZ_ERR_UNSUPPORTED;
+    return have_lzma2 && (nfilters == 1 || chain) ? XLZ_OK : XLZ_ERR_UNSUPPORTED;
 }
+
+int xz_index(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_blocks, size_t *n_blocks, xlz_filter_step *steps,
+             size_t max_steps, size_t *n_steps, uint64_t *total_uncompressed, bool chains);
 
 } // namespace
 
@@ -149,8 +163,27 @@ int parse_block_header(const uint8_t *p, size_t avail, size_t &hdr_size, uint32_
 extern "C" int xlz_xz_index(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_blocks, size_t *n_blocks,
                             uint64_t *total_uncompressed)
 {
+    return xz_index(file, len, blocks, max_blocks, n_blocks, nullptr, 0, nullptr, total_uncompressed, false);
+}
+
+// The same for files whose blocks may carry filter chains: the filters in front of a block's LZMA2 filter come back as
+// steps in the order a decoder applies them (the reverse of the header's), step.stream = the block's index.
+extern "C" int xlz_xz_index_chains(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_blocks, size_t *n_blocks,
+                                   xlz_filter_step *steps, size_t max_steps, size_t *n_steps, uint64_t *total_uncompressed)
+{
+    if (!n_steps || (!steps && max_steps)) return XLZ_ERR_BAD_ARG;
+    return xz_index(file, len, blocks, max_blocks, n_blocks, steps, max_steps, n_steps, total_uncompressed, true);
+}
+
+namespace {
+int xz_index(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_blocks, size_t *n_blocks, xlz_filter_step *steps,
+             size_t max_steps, size_t *n_steps, uint64_t *total_uncompressed, bool chains)
+{
     if (!file || !n_blocks || (!blocks && max_blocks)) return XLZ_ERR_BAD_ARG;
     *n_blocks = 0;
+    if (n_steps) *n_steps = 0;
+    size_t ns = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> chain;
     if (total_uncompressed) *total_uncompressed = 0;
     std::vector<Stream> streams;
     size_t end = len;
@@ -176,8 +209,14 @@ extern "C" int xlz_xz_index(const uint8_t *file, size_t len, xlz_xz_block *block
             uint64_t csz, usz;
             const uint64_t padded = (rec.first + 3) & ~3ull;
             if (pos > s.index_start || padded > s.index_start - pos) return XLZ_ERR_RESULT; // block inside the stream
-            const int st = parse_block_header(file + pos, s.index_start - pos, hdr, dict, csz, usz);
+            chain.clear();
+            const int st = parse_block_header(file + pos, s.index_start - pos, hdr, dict, csz, usz, chains ? &chain : nullptr);
             if (st != XLZ_OK) return st;
+            for (size_t k = chain.size(); k-- > 0; ns++)
+                if (ns < max_steps) {
+                    memset(&steps[ns], 0, sizeof steps[ns]);
+                    steps[ns].stream = nb, steps[ns].id = chain[k].first, steps[ns].param = chain[k].second;
+                }
             const unsigned chk = check_size(s.check);
             if (rec.first < hdr + chk) return XLZ_ERR_RESULT;
             const uint64_t comp = rec.first - hdr - chk;
@@ -202,9 +241,11 @@ extern "C" int xlz_xz_index(const uint8_t *file, size_t len, xlz_xz_block *block
         }
     }
     *n_blocks = nb;
+    if (n_steps) *n_steps = ns;
     if (total_uncompressed) *total_uncompressed = uoff;
-    return nb > max_blocks && max_blocks ? XLZ_ERR_OUT_CAP : XLZ_OK;
+    return (nb > max_blocks && max_blocks) || (ns > max_steps && max_steps) ? XLZ_ERR_OUT_CAP : XLZ_OK;
 }
+} // namespace
 
 // Whole file: index, one batch (block = raw LZMA2 stream, reader2.go:26-41), optional integrity
 // check of every block (CRC32 / CRC64 on host threads; other check types are left unverified
@@ -234,13 +275,16 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     if (!file || (!out && out_cap) || !out_len) return XLZ_ERR_BAD_ARG;
     *out_len = 0;
     if (unverified) *unverified = 0;
-    size_t nb = 0;
+    size_t nb = 0, nfs = 0;
     uint64_t total = 0;
-    int st = xlz_xz_index(file, len, nullptr, 0, &nb, &total);
+    // filter mode 1 (xlz_ctx_set_filter_mode; one context): blocks may carry Delta / BCJ filters; fs = their steps
+    const bool chains = n_ctx == 1 && xlz_ctx_filter_mode(ctxs[0]) == 1;
+    int st = xz_index(file, len, nullptr, 0, &nb, nullptr, 0, &nfs, &total, chains);
     if (st != XLZ_OK) return st;
     if (total > out_cap) return XLZ_ERR_OUT_CAP;
     std::vector<xlz_xz_block> blk(nb);
-    st = xlz_xz_index(file, len, blk.data(), nb, &nb, &total);
+    std::vector<xlz_filter_step> fs(nfs);
+    st = xz_index(file, len, blk.data(), nb, &nb, fs.data(), nfs, &nfs, &total, chains);
     if (st != XLZ_OK) return st;
     std::vector<xlz_stream_desc> d(nb);
     std::vector<xlz_result> r(nb);
@@ -272,8 +316,14 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         got.resize(cr.size());
         dg.assign(nb, 0);
         xlz_internal_check_stats_reset(ctxs[0]);
-        st = xlz_internal_decode_batch_checked(ctxs[0], d.data(), nb, r.data(), cr.data(), cr.size(), got.data(), 1);
+        if (chains) xlz_internal_filter_stats_reset(ctxs[0]);
+        st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, cr.data(), cr.size(), got.data(), 1)
+                 : xlz_internal_decode_batch_checked(ctxs[0], d.data(), nb, r.data(), cr.data(), cr.size(), got.data(), 1);
         for (size_t k = 0; k < of.size(); k++) dg[of[k]] = got[k];
+    } else if (chains) { // (the digests, if any, on host threads below: over the filtered bytes)
+        xlz_internal_filter_stats_reset(ctxs[0]);
+        st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, nullptr, 0, nullptr, 1)
+                 : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
     } else
         st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), nb, r.data()) : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
     if (st != XLZ_OK) return st;
