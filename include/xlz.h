@@ -269,11 +269,12 @@ void xlz_batch_destroy(xlz_batch *batch);
  * pool.  A range's digest covers [off, off + len) of its stream's output cut to [0, out_len) -- what the decoder produced
  * of it; an empty intersection gives 0, the CRC of no bytes.  Digests are the published CRCs (what zlib.crc32 and liblzma
  * give), CRC32 zero-extended to 64 bits.                                                              */
-enum { XLZ_CHECK_NONE = 0, XLZ_CHECK_CRC32 = 1, XLZ_CHECK_CRC64 = 4 }; /* the .xz check ids */
+enum { XLZ_CHECK_NONE = 0, XLZ_CHECK_CRC32 = 1, XLZ_CHECK_CRC64 = 4, XLZ_CHECK_SHA256 = 10 }; /* the .xz check ids */
 typedef struct xlz_check_range {
     uint64_t stream;   /* index into the call's / the batch's streams; >= n: XLZ_ERR_BAD_ARG for the call */
     uint64_t off, len; /* bytes of THAT STREAM'S OUTPUT                                               */
-    uint32_t kind;     /* XLZ_CHECK_CRC32 / XLZ_CHECK_CRC64, else XLZ_ERR_BAD_ARG                       */
+    uint32_t kind;     /* XLZ_CHECK_CRC32 / XLZ_CHECK_CRC64 (the _digests calls: XLZ_CHECK_SHA256 too), else
+                          XLZ_ERR_BAD_ARG                                                            */
     uint32_t reserved; /* 0, else XLZ_ERR_BAD_ARG                                                      */
 } xlz_check_range;
 /* Device-resident: waits for and collects the latest run like xlz_batch_results, runs the check kernels on the batch's
@@ -291,7 +292,9 @@ uint64_t xlz_crc64_combine(uint64_t crc_a, uint64_t crc_b, uint64_t len_b);
 /* Where xlz_xz_decode / xlz_7z_decode verify.  0 (default): on host threads after the call's download, as ever.  1: every
  * CRC32 / CRC64 block, folder and file (per-file ranges inside solid folders) through xlz_decode_batch_checked, digests
  * compared on the host; SHA-256 blocks, reserved check types and .7z Copy folders (never on the device) stay on the host.
- * Bytes, status and *unverified are the same in both modes.  xlz_xz_decode_multi / xlz_7z_decode_multi ignore the mode:
+ * 2: mode 1, and the SHA-256 blocks of an .xz file through xlz_decode_batch_digests: the device hashes the blocks that
+ * xlz_sha256_plan gives it, the host threads the others (a .7z archive has no SHA-256: there 2 is 1).
+ * Bytes, status and *unverified are the same in all modes.  xlz_xz_decode_multi / xlz_7z_decode_multi ignore the mode:
  * they check on the host.  Any other value: XLZ_ERR_BAD_ARG.                                              */
 int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode);
 int xlz_ctx_check_mode(const xlz_ctx *ctx);
@@ -364,6 +367,45 @@ typedef struct xlz_filter_stats {
     uint32_t reserved;
 } xlz_filter_stats;
 int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out);
+
+/* ---- SHA-256 on the device --------------------------------------------------------------------
+ * The third .xz check (id 10, what xz --check=sha256 writes), by a HIP kernel that gives every range a lane of its own:
+ * one SHA-256 is a serial chain, a batch has hundreds to tens of thousands of them (lzma_amd/csrc/xlz_sha256_dev.hip;
+ * DESIGN.md section 3.12).  The calls below are xlz_batch_checks / xlz_decode_batch_filtered with a digest format that
+ * holds 32 bytes and with kind XLZ_CHECK_SHA256 allowed, kinds mixed freely; the older calls keep refusing it.
+ *   CRC32 / CRC64: the published value little-endian in b[0..7], the rest 0.
+ *   SHA-256: the 32 bytes in FIPS 180-4 order, as an .xz block stores them; of an empty intersection, the SHA-256 of no
+ *   bytes (counted as empty_ranges).
+ * A lane is slow (tens of MB/s), a launch of thousands of ranges is fast: xlz_sha256_plan decides per call which SHA-256
+ * ranges the device takes; the others -- and the ranges of streams outside the arenas -- are hashed by host threads, over
+ * bytes downloaded for it (xlz_batch_digests) or over the caller's buffer (xlz_decode_batch_digests): host_ranges.     */
+typedef struct xlz_digest {
+    uint8_t b[32];
+} xlz_digest;
+int xlz_batch_digests(xlz_batch *batch, const xlz_check_range *ranges, size_t n, xlz_digest *out);
+int xlz_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                             const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                             xlz_digest *out);
+/* Host only, no device needed: which of n ranges of lens[] bytes the device should hash (on_device[i] = 1) and which the
+ * host (0).  The device's time is its longest range over the lane rate, times the rounds of lanes that run side by side;
+ * the host's is its bytes over host_threads x rate; ranges longer than a threshold go to the host, and the threshold is
+ * the one that minimises the larger time.  No range that would keep a launch busy for more than 0.5 s at the built-in
+ * lane rate is ever the device's.  host_threads 0: 16; a rate of 0: the built-in one (lzma_amd/csrc/xlz_sha256_dev.h says
+ * whether it is measured or still the instruction-count estimate).  NULL lens or on_device with n > 0: XLZ_ERR_BAD_ARG. */
+int xlz_sha256_plan(const uint64_t *lens, size_t n, uint32_t host_threads, double lane_bytes_per_s,
+                    double host_bytes_per_s_per_thread, uint8_t *on_device);
+/* Of the SHA-256 ranges of the most recent xlz_batch_digests / xlz_decode_batch_digests on `ctx`, or of the most recent
+ * xlz_xz_decode in check mode 2.  (xlz_check_stats counts them too, in its device / host / empty fields.)         */
+typedef struct xlz_sha256_stats {
+    uint64_t device_ranges, device_bytes; /* hashed by the kernel                                          */
+    uint64_t host_ranges, host_bytes;     /* hashed by host threads: the plan's choice, or streams outside the arenas */
+    uint64_t empty_ranges;
+    uint64_t threshold;  /* the longest range the plan gave the device (the largest over the launches; 0: none) */
+    double kernel_ms;    /* the kernel by HIP events, summed over the launches                            */
+    uint32_t launches;
+    uint32_t reserved;
+} xlz_sha256_stats;
+int xlz_ctx_last_sha256_stats(xlz_ctx *ctx, xlz_sha256_stats *out);
 
 /* ---- pull-style readers mirroring the reference's Go surface --------------- */
 /* Constructors take the compressed stream as a buffer (a Go shim slurps its io.Reader

@@ -13,7 +13,7 @@ from ._native import (EOF, ERR_BAD_ARG, ERR_CLOSED, ERR_DEVICE, ERR_HEADER_EOF, 
                       ERR_INSUFFICIENT_PROPS, ERR_NEED_ONE_READER, ERR_OUT_CAP, ERR_PROPS,
                       ERR_RC_INIT, ERR_RESULT, ERR_UNEXPECTED_EOF, ERR_UNSUPPORTED,
                       FMT_LZMA2_RAW, FMT_LZMA_ALONE, FMT_LZMA_RAW, NEED_INPUT, OK, OK_INPUT_EOF, UNKNOWN_SIZE,
-                      CHECK_CRC32, CHECK_CRC64, CHECK_NONE)
+                      CHECK_CRC32, CHECK_CRC64, CHECK_NONE, CHECK_SHA256)
 
 # the .xz filter ids (include/xlz.h: XLZ_FILTER_*)
 FILTER_DELTA, FILTER_X86, FILTER_POWERPC, FILTER_IA64, FILTER_ARM, FILTER_ARMTHUMB, FILTER_SPARC = 3, 4, 5, 6, 7, 8, 9
@@ -104,8 +104,9 @@ class Context:
         return n.value
 
     def set_check_mode(self, mode):
-        """where xz_decode / sevenzip_decode verify CRC32 / CRC64 (xlz_ctx_set_check_mode): 0 on host threads behind the
-        download (default), 1 on the device next to the decode"""
+        """where xz_decode / sevenzip_decode verify (xlz_ctx_set_check_mode): 0 on host threads behind the download
+        (default); 1 CRC32 / CRC64 on the device next to the decode; 2 as 1, and the SHA-256 blocks of an .xz file on the
+        device too, where sha256_plan gives them to it"""
         st = N.lib().xlz_ctx_set_check_mode(self._h, int(mode))
         if st != OK:
             raise LzmaError(st, "xlz_ctx_set_check_mode")
@@ -121,6 +122,15 @@ class Context:
         if st != OK:
             raise LzmaError(st, "xlz_ctx_last_check_stats")
         return {k: getattr(cs, k) for k, _ in N.CheckStats._fields_ if k != "reserved"}
+
+    def last_sha256_stats(self):
+        """who hashed the SHA-256 ranges of the last Batch.digests / decode_batch_digests / xz_decode in check mode 2 on this
+        context, and the threshold the plan chose (xlz_ctx_last_sha256_stats) -> dict"""
+        ss = N.Sha256Stats()
+        st = N.lib().xlz_ctx_last_sha256_stats(self._h, ctypes.byref(ss))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_sha256_stats")
+        return {k: getattr(ss, k) for k, _ in N.Sha256Stats._fields_ if k != "reserved"}
 
     def set_filter_mode(self, mode):
         """what xz_decode / sevenzip_decode do with Delta / BCJ filter chains (xlz_ctx_set_filter_mode): 0 refuse them
@@ -265,6 +275,42 @@ def decode_batch_filtered(ctx, streams, steps, checks=()):
         raise LzmaError(st, "xlz_decode_batch_filtered")
     del keep
     return [(outs[i].raw[: res[i].out_len], res[i].status, res[i].in_consumed) for i in range(n)], list(dig[: len(checks)])
+
+
+def _digest_values(ranges, dig):
+    """xlz_digest array -> an int per CRC range, 32 bytes per SHA-256 range"""
+    return [bytes(dig[q].b) if ranges[q][3] == CHECK_SHA256 else int.from_bytes(bytes(dig[q].b[:8]), "little")
+            for q in range(len(ranges))]
+
+
+def decode_batch_digests(ctx, streams, ranges, steps=()):
+    """decode_batch_filtered whose ranges may be CHECK_SHA256 too, kinds mixed (xlz_decode_batch_digests): a SHA-256 range
+    is hashed on the GPU, one lane per range, or by host threads, as sha256_plan splits the call's ranges.
+    -> (list of (output bytes, status, in_consumed), list of digests: int for a CRC, 32 bytes for a SHA-256)"""
+    streams, steps, ranges = list(streams), list(steps), list(ranges)
+    n = len(streams)
+    descs, keep, outs = _make_descs(streams)
+    res = (N.Result * max(n, 1))()
+    arr, _ = _make_ranges(ranges)
+    dig = (N.Digest * max(len(ranges), 1))()
+    st = N.lib().xlz_decode_batch_digests(ctx._h, descs, n, res, _make_steps(steps), len(steps), arr, len(ranges), dig)
+    if st != OK:
+        raise LzmaError(st, "xlz_decode_batch_digests")
+    del keep
+    return [(outs[i].raw[: res[i].out_len], res[i].status, res[i].in_consumed) for i in range(n)], _digest_values(ranges, dig)
+
+
+def sha256_plan(lens, host_threads=0, lane_rate=0, host_rate=0):
+    """which ranges of these lengths the device should hash -> list of bool (xlz_sha256_plan; host only).  lane_rate /
+    host_rate: bytes per second of one GPU lane / of one host thread, 0 for the built-in ones"""
+    lens = list(lens)
+    n = len(lens)
+    arr = (ctypes.c_uint64 * max(n, 1))(*lens)
+    on = (ctypes.c_uint8 * max(n, 1))()
+    st = N.lib().xlz_sha256_plan(arr, n, int(host_threads), float(lane_rate), float(host_rate), on)
+    if st != OK:
+        raise LzmaError(st, "xlz_sha256_plan")
+    return [bool(on[i]) for i in range(n)]
 
 
 def crc32_combine(crc_a, crc_b, len_b):
@@ -419,6 +465,32 @@ class Batch:
         if st != OK:
             raise LzmaError(st, "xlz_batch_checks")
         return list(dig[: len(ranges)])
+
+    def digests(self, ranges):
+        """checks() whose ranges may be CHECK_SHA256 too, kinds mixed (xlz_batch_digests) -> list of digests: int for a CRC,
+        32 bytes for a SHA-256.  The SHA-256 ranges sha256_plan leaves to the host are downloaded and hashed there."""
+        ranges = list(ranges)
+        arr, _ = _make_ranges(ranges)
+        dig = (N.Digest * max(len(ranges), 1))()
+        st = N.lib().xlz_batch_digests(self._h, arr, len(ranges), dig)
+        if st != OK:
+            raise LzmaError(st, "xlz_batch_digests")
+        return _digest_values(ranges, dig)
+
+    def _sha256_kernel(self, ranges):
+        """measuring aid (tools/sha256_bench.py): every range through the SHA-256 kernel whatever sha256_plan says
+        -> (list of 32-byte digests, kernel ms by HIP events)"""
+        ranges = list(ranges)
+        arr, _ = _make_ranges(ranges)
+        dig = (N.Digest * max(len(ranges), 1))()
+        ms = ctypes.c_double()
+        L = N.lib()
+        L.xlz_internal_batch_sha256_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(N.CheckRange), ctypes.c_size_t,
+                                                       ctypes.POINTER(N.Digest), ctypes.POINTER(ctypes.c_double)]
+        st = L.xlz_internal_batch_sha256_device(self._h, arr, len(ranges), dig, ctypes.byref(ms))
+        if st != OK:
+            raise LzmaError(st, "xlz_internal_batch_sha256_device")
+        return _digest_values(ranges, dig), ms.value
 
     def filter(self, steps):
         """undo filter steps in place on the decoded outputs, on the device (xlz_batch_filter): download, device_output and

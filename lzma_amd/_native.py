@@ -37,6 +37,7 @@ UNKNOWN_SIZE = 0xFFFFFFFFFFFFFFFF
 CHECK_NONE = 0
 CHECK_CRC32 = 1
 CHECK_CRC64 = 4
+CHECK_SHA256 = 10
 
 # every symbol include/xlz.h declares (tests check the .so exports all of them)
 EXPORTS = [
@@ -54,6 +55,7 @@ EXPORTS = [
     "xlz_ctx_check_mode", "xlz_ctx_last_check_stats",
     "xlz_filter_host", "xlz_batch_filter", "xlz_decode_batch_filtered", "xlz_ctx_set_filter_mode", "xlz_ctx_filter_mode",
     "xlz_ctx_last_filter_stats", "xlz_xz_index_chains", "xlz_7z_index_chains",
+    "xlz_batch_digests", "xlz_decode_batch_digests", "xlz_sha256_plan", "xlz_ctx_last_sha256_stats",
 ]
 
 
@@ -97,6 +99,16 @@ class CheckStats(ctypes.Structure):
     _fields_ = [("device_ranges", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_ranges", ctypes.c_uint64),
                 ("host_bytes", ctypes.c_uint64), ("empty_ranges", ctypes.c_uint64), ("kernel_ms", ctypes.c_double),
                 ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class Digest(ctypes.Structure):
+    _fields_ = [("b", ctypes.c_uint8 * 32)]
+
+
+class Sha256Stats(ctypes.Structure):
+    _fields_ = [("device_ranges", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_ranges", ctypes.c_uint64),
+                ("host_bytes", ctypes.c_uint64), ("empty_ranges", ctypes.c_uint64), ("threshold", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class FilterStep(ctypes.Structure):
@@ -290,6 +302,13 @@ def lib():
         L.xlz_7z_index_chains.argtypes = [vp, vp, sz, ctypes.POINTER(SzFolder), sz, ctypes.POINTER(sz), ctypes.POINTER(SzSubstream), sz,
                                           ctypes.POINTER(sz), ctypes.POINTER(FilterStep), sz, ctypes.POINTER(sz),
                                           ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "xlz_batch_digests"):  # (an older library loaded through XLZ_SO has no SHA-256 on the device)
+        L.xlz_batch_digests.argtypes = [vp, ctypes.POINTER(CheckRange), sz, ctypes.POINTER(Digest)]
+        L.xlz_decode_batch_digests.argtypes = [vp, ctypes.POINTER(StreamDesc), sz, ctypes.POINTER(Result), ctypes.POINTER(FilterStep), sz,
+                                               ctypes.POINTER(CheckRange), sz, ctypes.POINTER(Digest)]
+        L.xlz_sha256_plan.argtypes = [ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_uint32, ctypes.c_double, ctypes.c_double,
+                                      ctypes.POINTER(ctypes.c_uint8)]
+        L.xlz_ctx_last_sha256_stats.argtypes = [vp, ctypes.POINTER(Sha256Stats)]
     _lib = L
     return L
 

@@ -481,7 +481,7 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
     // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 of every file and folder that the batch decodes comes
     // from the device with the batch's results -- per-file ranges inside solid folders --, in the order the loop below
     // asks for them: dg[dg_first[i] ...] = folder i's files that carry a CRC, then the folder's own
-    const bool dev = verify && n_ctx <= 1 && ctx && xlz_ctx_check_mode(ctx) == 1;
+    const bool dev = verify && n_ctx <= 1 && ctx && xlz_ctx_check_mode(ctx) >= 1;
     std::vector<uint64_t> dg;
     std::vector<size_t> dg_first(fo.size(), 0);
     if (dev) {
@@ -735,7 +735,7 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     if (!file || (!out && out_cap) || !out_len) return XLZ_ERR_BAD_ARG;
     *out_len = 0;
     if (unverified) *unverified = 0;
-    if (verify && n_ctx == 1 && xlz_ctx_check_mode(ctx) == 1) xlz_internal_check_stats_reset(ctx); // (an encoded header's batch counts too)
+    if (verify && n_ctx == 1 && xlz_ctx_check_mode(ctx) >= 1) xlz_internal_check_stats_reset(ctx); // (an encoded header's batch counts too)
     Streams s;
     std::vector<uint8_t> dh;
     int st = main_streams(ctx, file, len, s, dh);

@@ -15,3 +15,8 @@ void xlz_internal_filter_stats_reset(xlz_ctx *ctx);
 int xlz_internal_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
                                        const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
                                        uint64_t *digests, int accumulate);
+// check mode 2: fresh SHA-256 statistics, and xlz_decode_batch_digests with accumulate
+void xlz_internal_sha256_stats_reset(xlz_ctx *ctx);
+int xlz_internal_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                      const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                                      xlz_digest *out, int accumulate);

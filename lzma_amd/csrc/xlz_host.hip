@@ -30,6 +30,7 @@
 #include "xlz_check.h"
 #include "xlz_check_dev.h"
 #include "xlz_check_host.h"
+#include "xlz_sha256_dev.h"
 #include "xlz_filter_dev.h"
 
 using namespace xlz;
@@ -244,6 +245,7 @@ struct xlz_ctx {
     hipStream_t check_stream = nullptr;
     int check_mode = 0;
     xlz_check_stats last_check = {}; // xlz_ctx_last_check_stats
+    xlz_sha256_stats last_sha = {};  // xlz_ctx_last_sha256_stats (xlz_sha256_dev.hip)
     // filters (xlz_filter_dev.hip): xlz_ctx_set_filter_mode, xlz_ctx_last_filter_stats
     int filter_mode = 0;
     xlz_filter_stats last_filter = {};
@@ -329,6 +331,10 @@ struct xlz_batch {
     uint8_t *d_chk = nullptr, *pin_chk = nullptr;
     size_t d_chk_cap = 0, pin_chk_cap = 0;
     hipEvent_t chk_ev0 = nullptr, chk_ev1 = nullptr;
+    // xlz_batch_digests / xlz_decode_batch_digests: digests | range table of the SHA-256 kernel on the device and in
+    // pinned memory (grow-only, kept until the batch goes)
+    uint8_t *d_sha = nullptr, *pin_sha = nullptr;
+    size_t sha_cap = 0;
     // xlz_batch_filter / xlz_decode_batch_filtered: step tables | window table | rows of sums on the device, the step tables
     // in pinned memory (grow-only, kept until the batch goes), and the events around the filter kernels
     uint8_t *d_flt = nullptr, *pin_flt = nullptr;
@@ -817,6 +823,8 @@ int batch_free(xlz_batch *b)
     batch_release(b, b->pin_chk, true);
     if (b->chk_ev0) (void)hipEventDestroy(b->chk_ev0);
     if (b->chk_ev1) (void)hipEventDestroy(b->chk_ev1);
+    batch_release(b, b->d_sha);
+    batch_release(b, b->pin_sha, true);
     batch_release(b, b->d_flt);
     batch_release(b, b->pin_flt, true);
     if (b->flt_ev0) (void)hipEventDestroy(b->flt_ev0);
@@ -1636,6 +1644,8 @@ extern "C" void xlz_batch_destroy(xlz_batch *b) { batch_free(b); }
 namespace xlz {
 int check_launch(int width, const uint8_t *arena, const xlzchk::DevRange *ranges, uint32_t n_ranges, uint32_t total_segs,
                  const void *tab, const void *consts, uint64_t *seg_vals, uint64_t *digests, int num_cus, hipStream_t stream);
+int sha256_launch(const uint8_t *arena, uint64_t arena_bytes, const xlzsha::DevRange *ranges, uint32_t n_ranges, uint32_t *digests,
+                  hipStream_t stream);
 }
 
 namespace {
@@ -1681,11 +1691,13 @@ int check_tables(xlz_ctx *ctx)
     return XLZ_OK;
 }
 
-int check_args(const xlz_check_range *ranges, size_t n_ranges, size_t n_streams, const uint64_t *digests)
+int check_args(const xlz_check_range *ranges, size_t n_ranges, size_t n_streams, const void *digests, bool sha_too = false)
 {
     if ((!ranges || !digests) && n_ranges) return XLZ_ERR_BAD_ARG;
     for (size_t q = 0; q < n_ranges; q++)
-        if (ranges[q].stream >= n_streams || (ranges[q].kind != XLZ_CHECK_CRC32 && ranges[q].kind != XLZ_CHECK_CRC64) || ranges[q].reserved)
+        if (ranges[q].stream >= n_streams ||
+            (ranges[q].kind != XLZ_CHECK_CRC32 && ranges[q].kind != XLZ_CHECK_CRC64 && !(sha_too && ranges[q].kind == XLZ_CHECK_SHA256)) ||
+            ranges[q].reserved)
             return XLZ_ERR_BAD_ARG;
     return XLZ_OK;
 }
@@ -1714,7 +1726,7 @@ int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
         const xlz_check_range &r = ranges[ri];
         const size_t s = (size_t)(r.stream - stream_base);
         const StreamPlan &pl = b->plans[s];
-        if (pl.oversize) continue;
+        if (pl.oversize || r.kind == XLZ_CHECK_SHA256) continue; // (SHA-256: batch_sha256_run)
         const bool in_arena = pl.host_status == 1;
         const uint64_t produced = in_arena ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : b->final_results[s].out_len;
         const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
@@ -1794,7 +1806,281 @@ int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
     return XLZ_OK;
 }
 
+// ---- SHA-256 (xlz_sha256_dev.hip) ----
+// xlz_sha256_plan: see include/xlz.h.  thr_out (optional): the longest length the device takes, 0 for none.
+void sha256_plan(const uint64_t *lens, size_t n, uint32_t host_threads, double lane_rate, double host_rate, uint8_t *on_device,
+                 uint64_t *thr_out)
+{
+    if (!host_threads) host_threads = xlzsha::kHostThreads;
+    if (!(lane_rate > 0)) lane_rate = xlzsha::kLaneBytesPerS;
+    if (!(host_rate > 0)) host_rate = xlzsha::kHostBytesPerSPerThread;
+    std::vector<uint64_t> s(lens, lens + n);
+    std::sort(s.begin(), s.end());
+    double total = 0;
+    for (uint64_t v : s) total += (double)v;
+    // the device takes the k shortest ranges; k only where the length changes.  k = 0: everything on the host.
+    double best = total / ((double)host_threads * host_rate), dev_bytes = 0;
+    uint64_t thr = 0;
+    for (size_t k = 1; k <= n; k++) {
+        if (s[k - 1] > xlzsha::kMaxDeviceLen) break; // (the cap of a launch, at the built-in rate whatever was passed)
+        dev_bytes += (double)s[k - 1];
+        if (k < n && s[k] == s[k - 1]) continue;
+        const double rounds = (double)((k + xlzsha::kRoundLanes - 1) / xlzsha::kRoundLanes);
+        const double dev_t = (double)s[k - 1] / lane_rate * rounds, host_t = (total - dev_bytes) / ((double)host_threads * host_rate);
+        const double t = std::max(dev_t, host_t);
+        if (t < best) best = t, thr = s[k - 1];
+    }
+    for (size_t i = 0; i < n; i++) on_device[i] = thr && lens[i] <= thr;
+    if (thr_out) *thr_out = thr;
+}
+
+// a range the host hashes: n bytes at p -> out
+struct ShaHostJob {
+    const uint8_t *p;
+    uint64_t n;
+    xlz_digest *out;
+};
+void sha256_host_jobs(const std::vector<ShaHostJob> &jobs)
+{
+    if (jobs.empty()) return;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const unsigned nth = (unsigned)std::min<size_t>(std::max(1u, std::min(hw ? hw : 1u, xlzsha::kHostThreads)), jobs.size());
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < jobs.size();) xlzcheck::sha256(jobs[i].p, (size_t)jobs[i].n, jobs[i].out->b);
+    };
+    std::vector<std::thread> th;
+    try {
+        for (unsigned t = 1; t < nth; t++) th.emplace_back(work);
+    } catch (...) { // (no thread to be had: this one does it all)
+    }
+    work();
+    for (auto &x : th) x.join();
+}
+void sha256_of_nothing(xlz_digest *out) { xlzcheck::sha256(out->b, 0, out->b); }
+void sha_stats_add(xlz_sha256_stats &t, const xlz_sha256_stats &a)
+{
+    t.device_ranges += a.device_ranges, t.device_bytes += a.device_bytes, t.host_ranges += a.host_ranges, t.host_bytes += a.host_bytes;
+    t.empty_ranges += a.empty_ranges, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
+    t.threshold = std::max(t.threshold, a.threshold);
+}
+// the SHA-256 ranges count in xlz_check_stats too
+void check_stats_add_sha(xlz_check_stats &t, const xlz_sha256_stats &a)
+{
+    t.device_ranges += a.device_ranges, t.device_bytes += a.device_bytes, t.host_ranges += a.host_ranges, t.host_bytes += a.host_bytes;
+    t.empty_ranges += a.empty_ranges, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
+}
+
+// batch_checks_run for the XLZ_CHECK_SHA256 ranges among ranges[idx[..]]: out[] is indexed like ranges[].  The plan splits
+// the ranges that lie in the arena; the device's are sorted longest first and run in launches of at most one round of
+// lanes (xlzsha::kRoundLanes) on `stream`, and are waited for.  The host's: `later` given (xlz_decode_batch_digests: the
+// caller's buffer is not filled yet) -- they are noted there, to be hashed over streams[].out when the call's downloads
+// are done, as are the ranges of streams outside the arena; else (a device-resident batch) their bytes are fetched and
+// hashed here.
+int batch_sha256_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *idx, size_t n_idx, size_t stream_base, xlz_digest *out,
+                     hipStream_t stream, const xlz_stream_desc *streams, std::vector<ShaHostJob> *later, xlz_sha256_stats &acc,
+                     bool all_on_device = false)
+{
+    using xlzsha::DevRange;
+    struct InArena {
+        size_t ri;
+        uint64_t off, len;
+    };
+    std::vector<InArena> cand;
+    for (size_t q = 0; q < n_idx; q++) {
+        const size_t ri = idx ? idx[q] : q;
+        const xlz_check_range &r = ranges[ri];
+        if (r.kind != XLZ_CHECK_SHA256) continue;
+        const size_t s = (size_t)(r.stream - stream_base);
+        const StreamPlan &pl = b->plans[s];
+        if (pl.oversize) continue; // (xlz_decode_batch settles those behind its batches)
+        const bool in_arena = pl.host_status == 1;
+        const uint64_t produced = in_arena ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : b->final_results[s].out_len;
+        const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
+        if (hi == lo) {
+            sha256_of_nothing(&out[ri]);
+            acc.empty_ranges++;
+        } else if (!in_arena) {
+            if (later && streams && streams[s].out && hi <= streams[s].out_cap) {
+                later->push_back(ShaHostJob{streams[s].out + lo, hi - lo, &out[ri]});
+                acc.host_ranges++, acc.host_bytes += hi - lo;
+            } else {
+                sha256_of_nothing(&out[ri]);
+                acc.empty_ranges++;
+            }
+        } else {
+            if (pl.out_off + hi > b->out_bytes) return XLZ_ERR_UNSUPPORTED;
+            cand.push_back(InArena{ri, pl.out_off + lo, hi - lo});
+        }
+    }
+    if (cand.empty()) return XLZ_OK;
+    std::vector<uint64_t> lens(cand.size());
+    std::vector<uint8_t> on_dev(cand.size());
+    for (size_t i = 0; i < cand.size(); i++) lens[i] = cand[i].len;
+    uint64_t thr = 0;
+    if (all_on_device) // (tools/sha256_bench.py: the kernel's rate on shapes the plan would refuse)
+        std::fill(on_dev.begin(), on_dev.end(), (uint8_t)1);
+    else
+        sha256_plan(lens.data(), lens.size(), 0, 0, 0, on_dev.data(), &thr);
+    acc.threshold = std::max(acc.threshold, thr);
+    std::vector<InArena> dev, host;
+    for (size_t i = 0; i < cand.size(); i++) (on_dev[i] ? dev : host).push_back(cand[i]);
+    std::stable_sort(dev.begin(), dev.end(), [](const InArena &x, const InArena &y) { return x.len > y.len; });
+    if (dev.size() > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+    xlz_ctx *ctx = b->ctx;
+    std::vector<std::vector<uint8_t>> fetched; // (device-resident batches: the bytes of the host's ranges)
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        if (!dev.empty()) {
+            const size_t dig_bytes = dev.size() * 32, tab_bytes = dev.size() * sizeof(DevRange);
+            if (b->sha_cap < dig_bytes + tab_bytes) {
+                batch_release(b, b->d_sha);
+                batch_release(b, b->pin_sha, true);
+                b->d_sha = b->pin_sha = nullptr, b->sha_cap = 0;
+                if (!batch_alloc(b, &b->d_sha, dig_bytes + tab_bytes) || !batch_alloc(b, &b->pin_sha, dig_bytes + tab_bytes, true))
+                    return XLZ_ERR_DEVICE;
+                b->sha_cap = dig_bytes + tab_bytes;
+            }
+            if (!b->chk_ev0) HIP_TRY(hipEventCreate(&b->chk_ev0));
+            if (!b->chk_ev1) HIP_TRY(hipEventCreate(&b->chk_ev1));
+            DevRange *h_tab = reinterpret_cast<DevRange *>(b->pin_sha + dig_bytes);
+            for (size_t i = 0; i < dev.size(); i++)
+                h_tab[i].off = dev[i].off, h_tab[i].len = dev[i].len, h_tab[i].out_index = (uint32_t)i, h_tab[i].reserved = 0;
+            DevRange *d_tab = reinterpret_cast<DevRange *>(b->d_sha + dig_bytes);
+            uint32_t *d_dig = reinterpret_cast<uint32_t *>(b->d_sha);
+            HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipEventRecord(b->chk_ev0, stream));
+            uint32_t launches = 0;
+            for (size_t at = 0; at < dev.size(); at += xlzsha::kRoundLanes, launches++) {
+                const uint32_t m = (uint32_t)std::min<size_t>(xlzsha::kRoundLanes, dev.size() - at);
+                if (xlz::sha256_launch(b->d_out, b->out_bytes, d_tab + at, m, d_dig, stream) != 0) {
+                    if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the SHA-256 kernel failed\n");
+                    (void)hipStreamSynchronize(stream);
+                    return XLZ_ERR_DEVICE;
+                }
+            }
+            HIP_TRY(hipEventRecord(b->chk_ev1, stream));
+            HIP_TRY(hipMemcpyAsync(b->pin_sha, d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, b->chk_ev0, b->chk_ev1));
+            for (size_t i = 0; i < dev.size(); i++) {
+                memcpy(out[dev[i].ri].b, b->pin_sha + 32 * i, 32);
+                acc.device_bytes += dev[i].len;
+            }
+            acc.device_ranges += dev.size(), acc.kernel_ms += ms, acc.launches += launches;
+        }
+        if (!later && !host.empty()) {
+            fetched.resize(host.size());
+            for (size_t i = 0; i < host.size(); i++) {
+                fetched[i].resize((size_t)host[i].len);
+                HIP_TRY(hipMemcpyAsync(fetched[i].data(), b->d_out + host[i].off, (size_t)host[i].len, hipMemcpyDeviceToHost, stream));
+            }
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    std::vector<ShaHostJob> now;
+    for (size_t i = 0; i < host.size(); i++) {
+        const size_t s = (size_t)(ranges[host[i].ri].stream - stream_base);
+        if (later && !(streams && streams[s].out)) { // (no buffer to read it from: as for a stream outside the arena)
+            sha256_of_nothing(&out[host[i].ri]);
+            acc.empty_ranges++;
+            continue;
+        }
+        acc.host_ranges++, acc.host_bytes += host[i].len;
+        if (later) // (the stream's bytes will be in the caller's buffer: the same range of it)
+            later->push_back(ShaHostJob{streams[s].out + (host[i].off - b->plans[s].out_off), host[i].len, &out[host[i].ri]});
+        else
+            now.push_back(ShaHostJob{fetched[i].data(), host[i].len, &out[host[i].ri]});
+    }
+    sha256_host_jobs(now);
+    return XLZ_OK;
+}
+
+void crc_digest(uint64_t v, xlz_digest *out)
+{
+    memset(out->b, 0, sizeof out->b);
+    for (int k = 0; k < 8; k++) out->b[k] = (uint8_t)(v >> (8 * k));
+}
+
 } // namespace
+
+extern "C" int xlz_sha256_plan(const uint64_t *lens, size_t n, uint32_t host_threads, double lane_bytes_per_s,
+                               double host_bytes_per_s_per_thread, uint8_t *on_device)
+{
+    if ((!lens || !on_device) && n) return XLZ_ERR_BAD_ARG;
+    if (n) sha256_plan(lens, n, host_threads, lane_bytes_per_s, host_bytes_per_s_per_thread, on_device, nullptr);
+    return XLZ_OK;
+}
+
+extern "C" int xlz_batch_digests(xlz_batch *b, const xlz_check_range *ranges, size_t n, xlz_digest *out)
+{
+    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
+    int st = check_args(ranges, n, b->n, out, true);
+    if (st != XLZ_OK) return st;
+    st = collect(b);
+    if (st != XLZ_OK) return st;
+    xlz_check_stats acc;
+    xlz_sha256_stats sha;
+    memset(&acc, 0, sizeof acc);
+    memset(&sha, 0, sizeof sha);
+    hipStream_t stream = b->run_stream ? b->run_stream : b->ctx->stream;
+    std::vector<uint64_t> crc(n);
+    st = batch_checks_run(b, ranges, nullptr, n, 0, crc.data(), stream, nullptr, acc);
+    if (st == XLZ_OK) st = batch_sha256_run(b, ranges, nullptr, n, 0, out, stream, nullptr, nullptr, sha);
+    if (st != XLZ_OK) return st;
+    for (size_t q = 0; q < n; q++)
+        if (ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &out[q]);
+    check_stats_add_sha(acc, sha);
+    std::lock_guard<std::mutex> lock(b->ctx->mu);
+    b->ctx->last_check = acc;
+    b->ctx->last_sha = sha;
+    return XLZ_OK;
+}
+
+extern "C" int xlz_ctx_last_sha256_stats(xlz_ctx *ctx, xlz_sha256_stats *out)
+{
+    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *out = ctx->last_sha;
+    return XLZ_OK;
+}
+// Measuring aids of tools/sha256_bench.py, not part of the C ABI: every SHA-256 range of a collected device-resident batch
+// through the kernel whatever the plan says (-> its time by HIP events), and `reps` hashes of the n bytes at p on `threads`
+// host threads (-> seconds).
+extern "C" int xlz_internal_batch_sha256_device(xlz_batch *b, const xlz_check_range *ranges, size_t n, xlz_digest *out, double *kernel_ms)
+{
+    if (!b || !b->ran || !kernel_ms) return XLZ_ERR_BAD_ARG;
+    int st = check_args(ranges, n, b->n, out, true);
+    if (st == XLZ_OK) st = collect(b);
+    if (st != XLZ_OK) return st;
+    xlz_sha256_stats sha;
+    memset(&sha, 0, sizeof sha);
+    st = batch_sha256_run(b, ranges, nullptr, n, 0, out, b->run_stream ? b->run_stream : b->ctx->stream, nullptr, nullptr, sha, true);
+    *kernel_ms = sha.kernel_ms;
+    return st;
+}
+extern "C" double xlz_internal_sha256_host_bench(const uint8_t *p, size_t n, size_t reps, uint32_t threads)
+{
+    std::vector<xlz_digest> out(reps);
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < reps;) xlzcheck::sha256(p, n, out[i].b);
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<std::thread> th;
+    for (uint32_t t = 1; t < threads; t++) th.emplace_back(work);
+    work();
+    for (auto &x : th) x.join();
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void xlz_internal_sha256_stats_reset(xlz_ctx *ctx)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    memset(&ctx->last_sha, 0, sizeof ctx->last_sha);
+}
 
 extern "C" int xlz_batch_checks(xlz_batch *b, const xlz_check_range *ranges, size_t n, uint64_t *digests)
 {
@@ -1820,7 +2106,7 @@ extern "C" uint64_t xlz_crc64_combine(uint64_t a, uint64_t b, uint64_t len_b) { 
 
 extern "C" int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode)
 {
-    if (!ctx || (mode != 0 && mode != 1)) return XLZ_ERR_BAD_ARG;
+    if (!ctx || (mode != 0 && mode != 1 && mode != 2)) return XLZ_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->check_mode = mode;
     return XLZ_OK;
@@ -2418,12 +2704,22 @@ extern "C" int xlz_decode_batch_plan(const xlz_stream_desc *streams, size_t n, s
 // still the call's.  A sub-batch that has steps never runs sliced: a sliced call ships every slice's bytes while the next
 // slice decodes, before any filter could see them (per-slice filtering with carried state is later work).
 static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const xlz_filter_step *steps,
-                             size_t n_steps, const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, bool accumulate)
+                             size_t n_steps, const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, bool accumulate,
+                             xlz_digest *xd = nullptr)
 {
     if (!ctx || (!streams && n) || (!results && n)) return XLZ_ERR_BAD_ARG;
     for (size_t i = 0; i < n; i++)
         if (!streams[i].out && streams[i].out_cap) return XLZ_ERR_BAD_ARG;
-    if (check_args(ranges, n_ranges, n, digests) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    if (check_args(ranges, n_ranges, n, xd ? (const void *)xd : (const void *)digests, xd != nullptr) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    // xd (xlz_decode_batch_digests): the CRCs go through a table of this call and are put into xd[] at the end; the SHA-256
+    // ranges run behind the CRC ranges of their sub-batch, those the host hashes when the call's bytes are in place
+    std::vector<uint64_t> crc_of(xd ? n_ranges : 0);
+    if (xd) digests = crc_of.data();
+    bool has_sha = false;
+    for (size_t q = 0; q < n_ranges && xd; q++) has_sha |= ranges[q].kind == XLZ_CHECK_SHA256;
+    std::vector<ShaHostJob> sha_later;
+    xlz_sha256_stats sha;
+    memset(&sha, 0, sizeof sha);
     if (filter_args(steps, n_steps, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
     for (size_t q = 0; q < n_steps; q++)
         if (streams[steps[q].stream].flags & XLZ_STREAM_F_LZMA2_SLICE) return XLZ_ERR_BAD_ARG; // (a filter needs the stream's start)
@@ -2551,6 +2847,9 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
         if (e == XLZ_OK && n_ranges && !sub_ranges[k].empty()) {
             e = batch_checks_run(sub[k], ranges, sub_ranges[k].data(), sub_ranges[k].size(), cuts[k], digests, ctx->check_stream,
                                  streams + cuts[k], chk);
+            if (e == XLZ_OK && has_sha)
+                e = batch_sha256_run(sub[k], ranges, sub_ranges[k].data(), sub_ranges[k].size(), cuts[k], xd, ctx->check_stream,
+                                     streams + cuts[k], &sha_later, sha);
             if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu checked at %.1f ms\n", k, now_ms());
             if (e != XLZ_OK) {
                 {
@@ -2724,13 +3023,28 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
             if (!std::binary_search(big.begin(), big.end(), (size_t)r.stream)) continue;
             const uint64_t produced = std::min<uint64_t>(results[r.stream].out_len, streams[r.stream].out_cap);
             const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
+            if (r.kind == XLZ_CHECK_SHA256) {
+                if (hi > lo)
+                    sha_later.push_back(ShaHostJob{streams[r.stream].out + lo, hi - lo, &xd[q]}), sha.host_ranges++, sha.host_bytes += hi - lo;
+                else
+                    sha256_of_nothing(&xd[q]), sha.empty_ranges++;
+                continue;
+            }
             digests[q] = hi > lo ? host_digest(r.kind, streams[r.stream].out + lo, hi - lo) : 0;
             if (hi > lo)
                 chk.host_ranges++, chk.host_bytes += hi - lo;
             else
                 chk.empty_ranges++;
         }
+        sha256_host_jobs(sha_later); // (every byte of the call is in the callers' buffers)
+        for (size_t q = 0; q < n_ranges && xd; q++)
+            if (ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(digests[q], &xd[q]);
+        check_stats_add_sha(chk, sha);
         std::lock_guard<std::mutex> lock(ctx->mu);
+        if (xd && accumulate)
+            sha_stats_add(ctx->last_sha, sha);
+        else if (xd)
+            ctx->last_sha = sha;
         if (accumulate) {
             xlz_check_stats &t = ctx->last_check;
             t.device_ranges += chk.device_ranges, t.device_bytes += chk.device_bytes, t.host_ranges += chk.host_ranges;
@@ -2767,6 +3081,21 @@ int xlz_internal_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *stre
                                        uint64_t *digests, int accumulate)
 {
     return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, digests, accumulate != 0);
+}
+
+extern "C" int xlz_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                        const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                                        xlz_digest *out)
+{
+    if (!ctx) return XLZ_ERR_BAD_ARG;
+    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, nullptr, false, out);
+}
+
+int xlz_internal_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
+                                      const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
+                                      xlz_digest *out, int accumulate)
+{
+    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, nullptr, accumulate != 0, out);
 }
 
 int xlz_internal_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,

@@ -299,14 +299,21 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     }
     // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 / CRC64 of every block comes from the device with the
     // batch's results, dg[i] = block i's digest; the other check types stay with the host threads below
-    const bool dev = verify && n_ctx == 1 && xlz_ctx_check_mode(ctxs[0]) == 1;
+    // check mode 2: the SHA-256 blocks join the range list, xdg[i] = block i's 32 bytes (the device's or the host's, as
+    // xlz_sha256_plan splits them)
+    const int cmode = verify && n_ctx == 1 ? xlz_ctx_check_mode(ctxs[0]) : 0;
+    const bool dev = cmode == 1 || cmode == 2;
+    bool dev_sha = false;
+    for (size_t i = 0; i < nb && cmode == 2; i++) dev_sha |= blk[i].check_type == 10;
+    if (cmode == 2) xlz_internal_sha256_stats_reset(ctxs[0]); // (the statistics of THIS call, also when it has no SHA-256 block)
     std::vector<uint64_t> dg;
+    std::vector<xlz_digest> xdg;
     if (dev) {
         std::vector<xlz_check_range> cr;
         std::vector<uint64_t> got;
         std::vector<size_t> of;
         for (size_t i = 0; i < nb; i++)
-            if (blk[i].check_type == 1 || blk[i].check_type == 4) {
+            if (blk[i].check_type == 1 || blk[i].check_type == 4 || (dev_sha && blk[i].check_type == 10)) {
                 xlz_check_range c;
                 memset(&c, 0, sizeof c);
                 c.stream = i, c.off = 0, c.len = blk[i].uncomp_len, c.kind = blk[i].check_type;
@@ -317,9 +324,19 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         dg.assign(nb, 0);
         xlz_internal_check_stats_reset(ctxs[0]);
         if (chains) xlz_internal_filter_stats_reset(ctxs[0]);
-        st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, cr.data(), cr.size(), got.data(), 1)
-                 : xlz_internal_decode_batch_checked(ctxs[0], d.data(), nb, r.data(), cr.data(), cr.size(), got.data(), 1);
-        for (size_t k = 0; k < of.size(); k++) dg[of[k]] = got[k];
+        if (dev_sha) {
+            std::vector<xlz_digest> xgot(cr.size());
+            xdg.resize(nb);
+            st = xlz_internal_decode_batch_digests(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, cr.data(), cr.size(), xgot.data(), 1);
+            for (size_t k = 0; k < of.size(); k++) {
+                xdg[of[k]] = xgot[k];
+                for (int j = 0; j < 8; j++) dg[of[k]] |= (uint64_t)xgot[k].b[j] << (8 * j); // (a CRC: little-endian in b[0..7])
+            }
+        } else {
+            st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, cr.data(), cr.size(), got.data(), 1)
+                     : xlz_internal_decode_batch_checked(ctxs[0], d.data(), nb, r.data(), cr.data(), cr.size(), got.data(), 1);
+            for (size_t k = 0; k < of.size(); k++) dg[of[k]] = got[k];
+        }
     } else if (chains) { // (the digests, if any, on host threads below: over the filtered bytes)
         xlz_internal_filter_stats_reset(ctxs[0]);
         st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, nullptr, 0, nullptr, 1)
@@ -346,6 +363,8 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
                     bad[i] = crc32(p, (size_t)blk[i].uncomp_len) != le32(c);
                 else if (blk[i].check_type == 4)
                     bad[i] = crc64(p, (size_t)blk[i].uncomp_len) != ((uint64_t)le32(c) | (uint64_t)le32(c + 4) << 32);
+                else if (blk[i].check_type == 10 && dev_sha)
+                    bad[i] = memcmp(xdg[i].b, c, 32) != 0;
                 else if (blk[i].check_type == 10) {
                     uint8_t dg[32];
                     xlzcheck::sha256(p, (size_t)blk[i].uncomp_len, dg);
@@ -358,7 +377,7 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         for (unsigned t = 1; t < nth; t++) th.emplace_back(work, t);
         work(0);
         for (auto &x : th) x.join();
-        if (dev)
+        if (dev && !dev_sha)
             for (size_t i = 0; i < nb; i++)
                 if (blk[i].check_type == 10) xlz_internal_check_stats_host(ctxs[0], 1, blk[i].uncomp_len);
         size_t nu = 0;
