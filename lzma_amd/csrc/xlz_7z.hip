@@ -508,13 +508,12 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
         }
         dg.resize(cr.size());
         if (!d.empty()) {
-            int st = fs.empty() ? xlz_internal_decode_batch_checked(ctx, d.data(), d.size(), r.data(), cr.data(), cr.size(), dg.data(), 1)
-                                : xlz_internal_decode_batch_filtered(ctx, d.data(), d.size(), r.data(), fs.data(), fs.size(), cr.data(),
-                                                                     cr.size(), dg.data(), 1);
+            int st = xlz_internal_decode_batch(ctx, d.data(), d.size(), r.data(),
+                                               PostWork{fs.data(), fs.size(), cr.data(), cr.size(), dg.data(), nullptr, true});
             if (st != XLZ_OK) return st;
         }
     } else if (!fs.empty()) { // (CRCs, if asked for, on host threads below: over the filtered bytes)
-        int st = xlz_internal_decode_batch_filtered(ctx, d.data(), d.size(), r.data(), fs.data(), fs.size(), nullptr, 0, nullptr, 1);
+        int st = xlz_internal_decode_batch(ctx, d.data(), d.size(), r.data(), PostWork{fs.data(), fs.size(), nullptr, 0, nullptr, nullptr, true});
         if (st != XLZ_OK) return st;
     } else if (!d.empty()) {
         int st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), d.size(), r.data())

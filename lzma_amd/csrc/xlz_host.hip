@@ -251,6 +251,17 @@ struct xlz_ctx {
     xlz_filter_stats last_filter = {};
 };
 
+// Scratch of one kind of post-decode kernel of a batch: device and pinned memory from where the batch's memory comes
+// (grow-only, kept until the batch goes), and the events around the kernels.
+struct xlz_batch;
+struct PostScratch {
+    uint8_t *dev = nullptr, *pin = nullptr;
+    size_t dev_cap = 0, pin_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int reserve(xlz_batch *b, size_t dev_bytes, size_t pin_bytes);
+    void release(xlz_batch *b);
+};
+
 // per-stream bookkeeping of a batch
 struct StreamPlan {
     int32_t host_status = 1; // 1 = decided on the device; otherwise final status from parsing
@@ -326,20 +337,10 @@ struct xlz_batch {
     hipEvent_t ev_heads = nullptr, ev_tails = nullptr;
     std::function<int()> upload_tails; // pending second half of the upload, run by xlz_batch_run behind the first launch
     PinLease in_lease;
-    // xlz_batch_checks / xlz_decode_batch_checked: range table | segment values | digests on the device, range table |
-    // digests in pinned memory (grow-only, kept until the batch goes), and the events around the check kernels
-    uint8_t *d_chk = nullptr, *pin_chk = nullptr;
-    size_t d_chk_cap = 0, pin_chk_cap = 0;
-    hipEvent_t chk_ev0 = nullptr, chk_ev1 = nullptr;
-    // xlz_batch_digests / xlz_decode_batch_digests: digests | range table of the SHA-256 kernel on the device and in
-    // pinned memory (grow-only, kept until the batch goes)
-    uint8_t *d_sha = nullptr, *pin_sha = nullptr;
-    size_t sha_cap = 0;
-    // xlz_batch_filter / xlz_decode_batch_filtered: step tables | window table | rows of sums on the device, the step tables
-    // in pinned memory (grow-only, kept until the batch goes), and the events around the filter kernels
-    uint8_t *d_flt = nullptr, *pin_flt = nullptr;
-    size_t d_flt_cap = 0, pin_flt_cap = 0;
-    hipEvent_t flt_ev0 = nullptr, flt_ev1 = nullptr;
+    // the post-decode stage's scratch (PostScratch), one per kind of kernel.  Checks: range table | segment values |
+    // digests on the device, range table | digests pinned.  SHA-256: digests | range table on both sides.  Filters: step
+    // tables | window table | rows of sums on the device, the step tables pinned.
+    PostScratch chk, sha, flt;
 };
 
 // ---------------------------------------------------------------- helpers ----
@@ -793,6 +794,33 @@ void batch_release(xlz_batch *b, void *p, bool pinned = false)
         (void)(pinned ? hipHostFree(p) : hipFree(p));
 }
 
+} // namespace
+
+// at least that much of each; a block that is too small goes back before the larger one is asked for
+int PostScratch::reserve(xlz_batch *b, size_t dev_bytes, size_t pin_bytes)
+{
+    auto grow = [&](uint8_t *&p, size_t &cap, size_t bytes, bool pinned) {
+        if (cap >= bytes) return true;
+        batch_release(b, p, pinned);
+        p = nullptr, cap = 0;
+        if (batch_alloc(b, &p, bytes, pinned)) cap = bytes;
+        return cap != 0;
+    };
+    if (!grow(dev, dev_cap, dev_bytes, false) || !grow(pin, pin_cap, pin_bytes, true)) return XLZ_ERR_DEVICE;
+    if (!ev0) HIP_TRY(hipEventCreate(&ev0));
+    if (!ev1) HIP_TRY(hipEventCreate(&ev1));
+    return XLZ_OK;
+}
+void PostScratch::release(xlz_batch *b)
+{
+    batch_release(b, dev);
+    batch_release(b, pin, true);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+}
+
+namespace {
+
 int batch_free(xlz_batch *b)
 {
     if (!b) return XLZ_OK;
@@ -819,16 +847,9 @@ int batch_free(xlz_batch *b)
     batch_release(b, b->d_pack);
     batch_release(b, b->d_res_snap);
     batch_release(b, b->pin_res, true);
-    batch_release(b, b->d_chk);
-    batch_release(b, b->pin_chk, true);
-    if (b->chk_ev0) (void)hipEventDestroy(b->chk_ev0);
-    if (b->chk_ev1) (void)hipEventDestroy(b->chk_ev1);
-    batch_release(b, b->d_sha);
-    batch_release(b, b->pin_sha, true);
-    batch_release(b, b->d_flt);
-    batch_release(b, b->pin_flt, true);
-    if (b->flt_ev0) (void)hipEventDestroy(b->flt_ev0);
-    if (b->flt_ev1) (void)hipEventDestroy(b->flt_ev1);
+    b->chk.release(b);
+    b->sha.release(b);
+    b->flt.release(b);
     delete b;
     return XLZ_OK;
 }
@@ -1707,6 +1728,34 @@ uint64_t host_digest(uint32_t kind, const uint8_t *p, uint64_t n)
     return kind == XLZ_CHECK_CRC32 ? (uint64_t)xlzcheck::crc32(p, (size_t)n) : xlzcheck::crc64(p, (size_t)n);
 }
 
+// stream s of a collected batch as xlzpost::clip sees it; `streams`: the batch's descriptors, where the callers' buffers
+// may be read
+xlzpost::StreamOut stream_out(const xlz_batch *b, size_t s, const xlz_stream_desc *streams)
+{
+    const StreamPlan &pl = b->plans[s];
+    return {b->final_results[s].out_len, pl.out_cap, pl.host_status == 1, pl.oversize, streams && streams[s].out ? streams[s].out_cap : 0};
+}
+
+// The kernels of one kind behind a collected batch, timed by the scratch's events: queue() puts the launches on `stream`
+// (false: one failed -- XLZ_DEBUG says which, by `what`; the stream is waited for all the same), then `bytes` at `src` on
+// the device go to `dst` (optional: the digests), then the stream is waited for.  *ms: the kernels' time.
+template <class Queue>
+int timed_bracket(hipStream_t stream, PostScratch &s, const char *what, float *ms, Queue queue, void *dst = nullptr, const void *src = nullptr,
+                  size_t bytes = 0)
+{
+    HIP_TRY(hipEventRecord(s.ev0, stream));
+    if (!queue()) {
+        if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the %s failed\n", what);
+        (void)hipStreamSynchronize(stream);
+        return XLZ_ERR_DEVICE;
+    }
+    HIP_TRY(hipEventRecord(s.ev1, stream));
+    if (bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipEventElapsedTime(ms, s.ev0, s.ev1));
+    return XLZ_OK;
+}
+
 // The digests of ranges[idx[0 .. n_idx)] (idx == nullptr: of ranges[0 .. n_idx)) of a COLLECTED batch, whose stream
 // `stream_base` is the batch's first: the ranges of streams in the output arena by the check kernels, queued on `stream`
 // -- the batch's own, or any other: collect() has waited for everything that writes the arena, its re-runs included --
@@ -1717,6 +1766,7 @@ int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
                      hipStream_t stream, const xlz_stream_desc *streams, xlz_check_stats &acc)
 {
     using xlzchk::DevRange;
+    using xlzpost::Place;
     if (!n_idx) return XLZ_OK;
     std::vector<DevRange> dev[2]; // CRC32, CRC64
     std::vector<size_t> where[2]; // ... and the index of each one's digest
@@ -1725,25 +1775,18 @@ int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
         const size_t ri = idx ? idx[q] : q;
         const xlz_check_range &r = ranges[ri];
         const size_t s = (size_t)(r.stream - stream_base);
-        const StreamPlan &pl = b->plans[s];
-        if (pl.oversize || r.kind == XLZ_CHECK_SHA256) continue; // (SHA-256: batch_sha256_run)
-        const bool in_arena = pl.host_status == 1;
-        const uint64_t produced = in_arena ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : b->final_results[s].out_len;
-        const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
+        const xlzpost::Clip c = xlzpost::clip(stream_out(b, s, streams), r.off, r.len);
+        if (c.place == Place::Oversize || r.kind == XLZ_CHECK_SHA256) continue; // (SHA-256: batch_sha256_run)
         digests[ri] = 0;
-        if (hi == lo) {
+        if (c.place == Place::Empty) {
             acc.empty_ranges++;
-        } else if (!in_arena) {
-            if (streams && streams[s].out && hi <= streams[s].out_cap) {
-                digests[ri] = host_digest(r.kind, streams[s].out + lo, hi - lo);
-                acc.host_ranges++, acc.host_bytes += hi - lo;
-            } else {
-                acc.empty_ranges++;
-            }
+        } else if (c.place == Place::Caller) {
+            digests[ri] = host_digest(r.kind, streams[s].out + c.lo, c.hi - c.lo);
+            acc.host_ranges++, acc.host_bytes += c.hi - c.lo;
         } else {
             const int k = r.kind == XLZ_CHECK_CRC64;
             DevRange d;
-            d.off = pl.out_off + lo, d.len = hi - lo;
+            d.off = b->plans[s].out_off + c.lo, d.len = c.hi - c.lo;
             const uint64_t ns = xlzchk::range_segments(d.off, d.len);
             if (d.off + d.len > b->out_bytes || segs[k] + ns > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
             d.seg_first = (uint32_t)segs[k], d.n_segs = (uint32_t)ns, d.out_index = (uint32_t)where[0].size() + (uint32_t)where[1].size(), d.reserved = 0;
@@ -1761,45 +1804,28 @@ int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
     HIP_TRY(hipSetDevice(ctx->device));
     int st = check_tables(ctx);
     if (st != XLZ_OK) return st;
-    // device: range table | segment values | digests; pinned: range table | digests
     const size_t tab_bytes = n_dev * sizeof(DevRange), seg_bytes = (size_t)(segs[0] + segs[1]) * 8, dig_bytes = n_dev * 8;
-    if (b->d_chk_cap < tab_bytes + seg_bytes + dig_bytes) {
-        batch_release(b, b->d_chk);
-        b->d_chk = nullptr, b->d_chk_cap = 0;
-        const size_t want = tab_bytes + seg_bytes + dig_bytes;
-        if (!batch_alloc(b, &b->d_chk, want)) return XLZ_ERR_DEVICE;
-        b->d_chk_cap = want;
-    }
-    if (b->pin_chk_cap < tab_bytes + dig_bytes) {
-        batch_release(b, b->pin_chk, true);
-        b->pin_chk = nullptr, b->pin_chk_cap = 0;
-        if (!batch_alloc(b, &b->pin_chk, tab_bytes + dig_bytes, true)) return XLZ_ERR_DEVICE;
-        b->pin_chk_cap = tab_bytes + dig_bytes;
-    }
-    if (!b->chk_ev0) HIP_TRY(hipEventCreate(&b->chk_ev0));
-    if (!b->chk_ev1) HIP_TRY(hipEventCreate(&b->chk_ev1));
-    DevRange *h_tab = reinterpret_cast<DevRange *>(b->pin_chk);
-    uint64_t *h_dig = reinterpret_cast<uint64_t *>(b->pin_chk + tab_bytes);
+    st = b->chk.reserve(b, tab_bytes + seg_bytes + dig_bytes, tab_bytes + dig_bytes);
+    if (st != XLZ_OK) return st;
+    DevRange *h_tab = reinterpret_cast<DevRange *>(b->chk.pin);
+    uint64_t *h_dig = reinterpret_cast<uint64_t *>(b->chk.pin + tab_bytes);
     if (!dev[0].empty()) memcpy(h_tab, dev[0].data(), dev[0].size() * sizeof(DevRange));
     if (!dev[1].empty()) memcpy(h_tab + dev[0].size(), dev[1].data(), dev[1].size() * sizeof(DevRange));
-    DevRange *d_tab = reinterpret_cast<DevRange *>(b->d_chk);
-    uint64_t *d_seg = reinterpret_cast<uint64_t *>(b->d_chk + tab_bytes);
-    uint64_t *d_dig = reinterpret_cast<uint64_t *>(b->d_chk + tab_bytes + seg_bytes);
+    DevRange *d_tab = reinterpret_cast<DevRange *>(b->chk.dev);
+    uint64_t *d_seg = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes);
+    uint64_t *d_dig = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes + seg_bytes);
     HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(b->chk_ev0, stream));
-    if (xlz::check_launch(32, b->d_out, d_tab, (uint32_t)dev[0].size(), (uint32_t)segs[0], ctx->chk_tab[0], ctx->chk_consts[0], d_seg, d_dig,
-                          ctx->num_cus, stream) != 0 ||
-        xlz::check_launch(64, b->d_out, d_tab + dev[0].size(), (uint32_t)dev[1].size(), (uint32_t)segs[1], ctx->chk_tab[1], ctx->chk_consts[1],
-                          d_seg + segs[0], d_dig, ctx->num_cus, stream) != 0) {
-        if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the check kernels failed\n");
-        (void)hipStreamSynchronize(stream);
-        return XLZ_ERR_DEVICE;
-    }
-    HIP_TRY(hipEventRecord(b->chk_ev1, stream));
-    HIP_TRY(hipMemcpyAsync(h_dig, d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, b->chk_ev0, b->chk_ev1));
+    st = timed_bracket(
+        stream, b->chk, "check kernels", &ms,
+        [&] {
+            return xlz::check_launch(32, b->d_out, d_tab, (uint32_t)dev[0].size(), (uint32_t)segs[0], ctx->chk_tab[0], ctx->chk_consts[0], d_seg,
+                                     d_dig, ctx->num_cus, stream) == 0 &&
+                   xlz::check_launch(64, b->d_out, d_tab + dev[0].size(), (uint32_t)dev[1].size(), (uint32_t)segs[1], ctx->chk_tab[1],
+                                     ctx->chk_consts[1], d_seg + segs[0], d_dig, ctx->num_cus, stream) == 0;
+        },
+        h_dig, d_dig, dig_bytes);
+    if (st != XLZ_OK) return st;
     for (int k = 0; k < 2; k++)
         for (size_t j = 0; j < dev[k].size(); j++) digests[where[k][j]] = h_dig[dev[k][j].out_index];
     acc.device_ranges += n_dev, acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches++;
@@ -1858,17 +1884,23 @@ void sha256_host_jobs(const std::vector<ShaHostJob> &jobs)
     for (auto &x : th) x.join();
 }
 void sha256_of_nothing(xlz_digest *out) { xlzcheck::sha256(out->b, 0, out->b); }
-void sha_stats_add(xlz_sha256_stats &t, const xlz_sha256_stats &a)
+
+// the statistics of a finished call become the context's: `tag` is what xlzpost::stats_add wants behind its two operands
+template <class T, class... Tag> void publish(xlz_ctx *ctx, T xlz_ctx::*member, const T &v, bool accumulate, Tag... tag)
 {
-    t.device_ranges += a.device_ranges, t.device_bytes += a.device_bytes, t.host_ranges += a.host_ranges, t.host_bytes += a.host_bytes;
-    t.empty_ranges += a.empty_ranges, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
-    t.threshold = std::max(t.threshold, a.threshold);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (accumulate)
+        xlzpost::stats_add(ctx->*member, v, tag...);
+    else
+        ctx->*member = v;
 }
-// the SHA-256 ranges count in xlz_check_stats too
-void check_stats_add_sha(xlz_check_stats &t, const xlz_sha256_stats &a)
+// ... and are read: xlz_ctx_last_check_stats, xlz_ctx_last_sha256_stats, xlz_ctx_last_filter_stats
+template <class T> int last_stats(xlz_ctx *ctx, T xlz_ctx::*member, T *out)
 {
-    t.device_ranges += a.device_ranges, t.device_bytes += a.device_bytes, t.host_ranges += a.host_ranges, t.host_bytes += a.host_bytes;
-    t.empty_ranges += a.empty_ranges, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
+    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *out = ctx->*member;
+    return XLZ_OK;
 }
 
 // batch_checks_run for the XLZ_CHECK_SHA256 ranges among ranges[idx[..]]: out[] is indexed like ranges[].  The plan splits
@@ -1882,6 +1914,7 @@ int batch_sha256_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
                      bool all_on_device = false)
 {
     using xlzsha::DevRange;
+    using xlzpost::Place;
     struct InArena {
         size_t ri;
         uint64_t off, len;
@@ -1892,25 +1925,17 @@ int batch_sha256_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
         const xlz_check_range &r = ranges[ri];
         if (r.kind != XLZ_CHECK_SHA256) continue;
         const size_t s = (size_t)(r.stream - stream_base);
-        const StreamPlan &pl = b->plans[s];
-        if (pl.oversize) continue; // (xlz_decode_batch settles those behind its batches)
-        const bool in_arena = pl.host_status == 1;
-        const uint64_t produced = in_arena ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : b->final_results[s].out_len;
-        const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
-        if (hi == lo) {
+        const xlzpost::Clip c = xlzpost::clip(stream_out(b, s, later ? streams : nullptr), r.off, r.len);
+        if (c.place == Place::Oversize) continue; // (xlz_decode_batch settles those behind its batches)
+        if (c.place == Place::Empty) {
             sha256_of_nothing(&out[ri]);
             acc.empty_ranges++;
-        } else if (!in_arena) {
-            if (later && streams && streams[s].out && hi <= streams[s].out_cap) {
-                later->push_back(ShaHostJob{streams[s].out + lo, hi - lo, &out[ri]});
-                acc.host_ranges++, acc.host_bytes += hi - lo;
-            } else {
-                sha256_of_nothing(&out[ri]);
-                acc.empty_ranges++;
-            }
+        } else if (c.place == Place::Caller) {
+            later->push_back(ShaHostJob{streams[s].out + c.lo, c.hi - c.lo, &out[ri]});
+            acc.host_ranges++, acc.host_bytes += c.hi - c.lo;
         } else {
-            if (pl.out_off + hi > b->out_bytes) return XLZ_ERR_UNSUPPORTED;
-            cand.push_back(InArena{ri, pl.out_off + lo, hi - lo});
+            if (b->plans[s].out_off + c.hi > b->out_bytes) return XLZ_ERR_UNSUPPORTED;
+            cand.push_back(InArena{ri, b->plans[s].out_off + c.lo, c.hi - c.lo});
         }
     }
     if (cand.empty()) return XLZ_OK;
@@ -1934,39 +1959,29 @@ int batch_sha256_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
         HIP_TRY(hipSetDevice(ctx->device));
         if (!dev.empty()) {
             const size_t dig_bytes = dev.size() * 32, tab_bytes = dev.size() * sizeof(DevRange);
-            if (b->sha_cap < dig_bytes + tab_bytes) {
-                batch_release(b, b->d_sha);
-                batch_release(b, b->pin_sha, true);
-                b->d_sha = b->pin_sha = nullptr, b->sha_cap = 0;
-                if (!batch_alloc(b, &b->d_sha, dig_bytes + tab_bytes) || !batch_alloc(b, &b->pin_sha, dig_bytes + tab_bytes, true))
-                    return XLZ_ERR_DEVICE;
-                b->sha_cap = dig_bytes + tab_bytes;
-            }
-            if (!b->chk_ev0) HIP_TRY(hipEventCreate(&b->chk_ev0));
-            if (!b->chk_ev1) HIP_TRY(hipEventCreate(&b->chk_ev1));
-            DevRange *h_tab = reinterpret_cast<DevRange *>(b->pin_sha + dig_bytes);
+            int st = b->sha.reserve(b, dig_bytes + tab_bytes, dig_bytes + tab_bytes);
+            if (st != XLZ_OK) return st;
+            DevRange *h_tab = reinterpret_cast<DevRange *>(b->sha.pin + dig_bytes);
             for (size_t i = 0; i < dev.size(); i++)
                 h_tab[i].off = dev[i].off, h_tab[i].len = dev[i].len, h_tab[i].out_index = (uint32_t)i, h_tab[i].reserved = 0;
-            DevRange *d_tab = reinterpret_cast<DevRange *>(b->d_sha + dig_bytes);
-            uint32_t *d_dig = reinterpret_cast<uint32_t *>(b->d_sha);
+            DevRange *d_tab = reinterpret_cast<DevRange *>(b->sha.dev + dig_bytes);
+            uint32_t *d_dig = reinterpret_cast<uint32_t *>(b->sha.dev);
             HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipEventRecord(b->chk_ev0, stream));
             uint32_t launches = 0;
-            for (size_t at = 0; at < dev.size(); at += xlzsha::kRoundLanes, launches++) {
-                const uint32_t m = (uint32_t)std::min<size_t>(xlzsha::kRoundLanes, dev.size() - at);
-                if (xlz::sha256_launch(b->d_out, b->out_bytes, d_tab + at, m, d_dig, stream) != 0) {
-                    if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the SHA-256 kernel failed\n");
-                    (void)hipStreamSynchronize(stream);
-                    return XLZ_ERR_DEVICE;
-                }
-            }
-            HIP_TRY(hipEventRecord(b->chk_ev1, stream));
-            HIP_TRY(hipMemcpyAsync(b->pin_sha, d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
             float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, b->chk_ev0, b->chk_ev1));
+            st = timed_bracket(
+                stream, b->sha, "SHA-256 kernel", &ms,
+                [&] {
+                    for (size_t at = 0; at < dev.size(); at += xlzsha::kRoundLanes, launches++) {
+                        const uint32_t m = (uint32_t)std::min<size_t>(xlzsha::kRoundLanes, dev.size() - at);
+                        if (xlz::sha256_launch(b->d_out, b->out_bytes, d_tab + at, m, d_dig, stream) != 0) return false;
+                    }
+                    return true;
+                },
+                b->sha.pin, d_dig, dig_bytes);
+            if (st != XLZ_OK) return st;
             for (size_t i = 0; i < dev.size(); i++) {
-                memcpy(out[dev[i].ri].b, b->pin_sha + 32 * i, 32);
+                memcpy(out[dev[i].ri].b, b->sha.pin + 32 * i, 32);
                 acc.device_bytes += dev[i].len;
             }
             acc.device_ranges += dev.size(), acc.kernel_ms += ms, acc.launches += launches;
@@ -2004,6 +2019,17 @@ void crc_digest(uint64_t v, xlz_digest *out)
     for (int k = 0; k < 8; k++) out->b[k] = (uint8_t)(v >> (8 * k));
 }
 
+// What the xlz_batch_* calls of the post-decode kernels begin with: the batch has run, args(streams of the batch) accepts
+// the call's tables, the results are collected (nothing writes the arena any more).  *stream: where their kernels go.
+template <class Args> int batch_post_begin(xlz_batch *b, Args args, hipStream_t *stream)
+{
+    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
+    int st = args(b->n);
+    if (st == XLZ_OK) st = collect(b);
+    *stream = b->run_stream ? b->run_stream : b->ctx->stream;
+    return st;
+}
+
 } // namespace
 
 extern "C" int xlz_sha256_plan(const uint64_t *lens, size_t n, uint32_t host_threads, double lane_bytes_per_s,
@@ -2016,48 +2042,34 @@ extern "C" int xlz_sha256_plan(const uint64_t *lens, size_t n, uint32_t host_thr
 
 extern "C" int xlz_batch_digests(xlz_batch *b, const xlz_check_range *ranges, size_t n, xlz_digest *out)
 {
-    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
-    int st = check_args(ranges, n, b->n, out, true);
+    hipStream_t stream;
+    int st = batch_post_begin(b, [&](size_t streams) { return check_args(ranges, n, streams, out, true); }, &stream);
     if (st != XLZ_OK) return st;
-    st = collect(b);
-    if (st != XLZ_OK) return st;
-    xlz_check_stats acc;
-    xlz_sha256_stats sha;
-    memset(&acc, 0, sizeof acc);
-    memset(&sha, 0, sizeof sha);
-    hipStream_t stream = b->run_stream ? b->run_stream : b->ctx->stream;
+    xlz_check_stats acc = {};
+    xlz_sha256_stats sha = {};
     std::vector<uint64_t> crc(n);
     st = batch_checks_run(b, ranges, nullptr, n, 0, crc.data(), stream, nullptr, acc);
     if (st == XLZ_OK) st = batch_sha256_run(b, ranges, nullptr, n, 0, out, stream, nullptr, nullptr, sha);
     if (st != XLZ_OK) return st;
     for (size_t q = 0; q < n; q++)
         if (ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &out[q]);
-    check_stats_add_sha(acc, sha);
-    std::lock_guard<std::mutex> lock(b->ctx->mu);
-    b->ctx->last_check = acc;
-    b->ctx->last_sha = sha;
+    xlzpost::stats_add(acc, sha); // (the SHA-256 ranges count in xlz_check_stats too)
+    publish(b->ctx, &xlz_ctx::last_check, acc, false);
+    publish(b->ctx, &xlz_ctx::last_sha, sha, false);
     return XLZ_OK;
 }
 
-extern "C" int xlz_ctx_last_sha256_stats(xlz_ctx *ctx, xlz_sha256_stats *out)
-{
-    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    *out = ctx->last_sha;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_last_sha256_stats(xlz_ctx *ctx, xlz_sha256_stats *out) { return last_stats(ctx, &xlz_ctx::last_sha, out); }
 // Measuring aids of tools/sha256_bench.py, not part of the C ABI: every SHA-256 range of a collected device-resident batch
 // through the kernel whatever the plan says (-> its time by HIP events), and `reps` hashes of the n bytes at p on `threads`
 // host threads (-> seconds).
 extern "C" int xlz_internal_batch_sha256_device(xlz_batch *b, const xlz_check_range *ranges, size_t n, xlz_digest *out, double *kernel_ms)
 {
-    if (!b || !b->ran || !kernel_ms) return XLZ_ERR_BAD_ARG;
-    int st = check_args(ranges, n, b->n, out, true);
-    if (st == XLZ_OK) st = collect(b);
+    hipStream_t stream;
+    int st = !kernel_ms ? XLZ_ERR_BAD_ARG : batch_post_begin(b, [&](size_t streams) { return check_args(ranges, n, streams, out, true); }, &stream);
     if (st != XLZ_OK) return st;
-    xlz_sha256_stats sha;
-    memset(&sha, 0, sizeof sha);
-    st = batch_sha256_run(b, ranges, nullptr, n, 0, out, b->run_stream ? b->run_stream : b->ctx->stream, nullptr, nullptr, sha, true);
+    xlz_sha256_stats sha = {};
+    st = batch_sha256_run(b, ranges, nullptr, n, 0, out, stream, nullptr, nullptr, sha, true);
     *kernel_ms = sha.kernel_ms;
     return st;
 }
@@ -2076,26 +2088,17 @@ extern "C" double xlz_internal_sha256_host_bench(const uint8_t *p, size_t n, siz
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-void xlz_internal_sha256_stats_reset(xlz_ctx *ctx)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    memset(&ctx->last_sha, 0, sizeof ctx->last_sha);
-}
+void xlz_internal_sha256_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_sha, xlz_sha256_stats{}, false); }
 
 extern "C" int xlz_batch_checks(xlz_batch *b, const xlz_check_range *ranges, size_t n, uint64_t *digests)
 {
-    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
-    int st = check_args(ranges, n, b->n, digests);
+    hipStream_t stream;
+    int st = batch_post_begin(b, [&](size_t streams) { return check_args(ranges, n, streams, digests); }, &stream);
     if (st != XLZ_OK) return st;
-    st = collect(b);
-    if (st != XLZ_OK) return st;
-    xlz_check_stats acc;
-    memset(&acc, 0, sizeof acc);
-    st = batch_checks_run(b, ranges, nullptr, n, 0, digests, b->run_stream ? b->run_stream : b->ctx->stream, nullptr, acc);
-    if (st != XLZ_OK) return st;
-    std::lock_guard<std::mutex> lock(b->ctx->mu);
-    b->ctx->last_check = acc;
-    return XLZ_OK;
+    xlz_check_stats acc = {};
+    st = batch_checks_run(b, ranges, nullptr, n, 0, digests, stream, nullptr, acc);
+    if (st == XLZ_OK) publish(b->ctx, &xlz_ctx::last_check, acc, false);
+    return st;
 }
 
 extern "C" uint32_t xlz_crc32_combine(uint32_t a, uint32_t b, uint64_t len_b)
@@ -2113,19 +2116,9 @@ extern "C" int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode)
 }
 extern "C" int xlz_ctx_check_mode(const xlz_ctx *ctx) { return ctx ? ctx->check_mode : XLZ_ERR_BAD_ARG; }
 
-extern "C" int xlz_ctx_last_check_stats(xlz_ctx *ctx, xlz_check_stats *out)
-{
-    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    *out = ctx->last_check;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_last_check_stats(xlz_ctx *ctx, xlz_check_stats *out) { return last_stats(ctx, &xlz_ctx::last_check, out); }
 
-void xlz_internal_check_stats_reset(xlz_ctx *ctx)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    memset(&ctx->last_check, 0, sizeof ctx->last_check);
-}
+void xlz_internal_check_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_check, xlz_check_stats{}, false); }
 void xlz_internal_check_stats_host(xlz_ctx *ctx, uint64_t ranges, uint64_t bytes)
 {
     std::lock_guard<std::mutex> lock(ctx->mu);
@@ -2157,12 +2150,6 @@ int filter_args(const xlz_filter_step *steps, size_t n_steps, size_t n_streams)
     return XLZ_OK;
 }
 
-void filter_stats_add(xlz_filter_stats &t, const xlz_filter_stats &a)
-{
-    t.device_steps += a.device_steps, t.device_bytes += a.device_bytes, t.host_steps += a.host_steps, t.host_bytes += a.host_bytes;
-    t.empty_steps += a.empty_steps, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
-}
-
 // Applies steps[idx[0 .. n_idx)] (idx == nullptr: steps[0 .. n_idx)) to the streams of a COLLECTED batch whose stream
 // `stream_base` is the batch's first, in place in the output arena: collect() has waited for everything that writes the
 // arena, its re-runs included.  Round r of launches takes the r-th step of every stream that has one; all rounds are
@@ -2184,12 +2171,13 @@ int batch_filter_run(xlz_batch *b, const xlz_filter_step *steps, const size_t *i
         const xlz_filter_step &f = steps[idx ? idx[q] : q];
         const size_t s = (size_t)(f.stream - stream_base);
         const StreamPlan &pl = b->plans[s];
-        if (pl.oversize) continue;
-        const uint64_t produced = pl.host_status == 1 ? std::min<uint64_t>(b->final_results[s].out_len, pl.out_cap) : 0;
-        if (!produced) {
+        const xlzpost::Clip whole = xlzpost::clip(stream_out(b, s, nullptr), 0, xlzpost::kWholeStream);
+        if (whole.place == xlzpost::Place::Oversize) continue;
+        if (whole.place != xlzpost::Place::Arena) {
             acc.empty_steps++;
             continue;
         }
+        const uint64_t produced = whole.hi;
         if (depth[s] >= kMaxStepsPerStream || pl.out_off + produced > b->out_bytes || (pl.out_off & 15)) return XLZ_ERR_UNSUPPORTED;
         Round &R = rounds[depth[s]++];
         const int cls = f.id == XLZ_FILTER_X86 ? 1 : f.id == XLZ_FILTER_DELTA ? 2 : 0;
@@ -2223,52 +2211,36 @@ int batch_filter_run(xlz_batch *b, const xlz_filter_step *steps, const size_t *i
     std::lock_guard<std::mutex> lock(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t tab_room = align_up(tab_bytes, 256);
-    if (b->d_flt_cap < tab_room + scratch_bytes) {
-        batch_release(b, b->d_flt);
-        b->d_flt = nullptr, b->d_flt_cap = 0;
-        if (!batch_alloc(b, &b->d_flt, tab_room + scratch_bytes)) return XLZ_ERR_DEVICE;
-        b->d_flt_cap = tab_room + scratch_bytes;
-    }
-    if (b->pin_flt_cap < tab_bytes) {
-        batch_release(b, b->pin_flt, true);
-        b->pin_flt = nullptr, b->pin_flt_cap = 0;
-        if (!batch_alloc(b, &b->pin_flt, tab_bytes, true)) return XLZ_ERR_DEVICE;
-        b->pin_flt_cap = tab_bytes;
-    }
-    if (!b->flt_ev0) HIP_TRY(hipEventCreate(&b->flt_ev0));
-    if (!b->flt_ev1) HIP_TRY(hipEventCreate(&b->flt_ev1));
+    int st = b->flt.reserve(b, tab_room + scratch_bytes, tab_bytes);
+    if (st != XLZ_OK) return st;
     size_t at = 0;
     for (const Round &R : rounds)
         for (int c = 0; c < 3; c++)
             if (!R.tab[c].empty()) {
-                memcpy(b->pin_flt + at, R.tab[c].data(), R.tab[c].size() * sizeof(DevStep));
+                memcpy(b->flt.pin + at, R.tab[c].data(), R.tab[c].size() * sizeof(DevStep));
                 at += R.tab[c].size() * sizeof(DevStep);
             }
-    HIP_TRY(hipMemcpyAsync(b->d_flt, b->pin_flt, tab_bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(b->flt_ev0, stream));
-    uint8_t *d_scratch = b->d_flt + tab_room;
+    HIP_TRY(hipMemcpyAsync(b->flt.dev, b->flt.pin, tab_bytes, hipMemcpyHostToDevice, stream));
+    uint8_t *d_scratch = b->flt.dev + tab_room;
     uint32_t launches = 0;
-    at = 0;
-    for (const Round &R : rounds) {
-        uint8_t *d_rows = d_scratch + align_up((size_t)R.windows * 2, 256);
-        for (int c = 0; c < 3; c++) {
-            if (R.tab[c].empty()) continue;
-            const int k = xlz::filter_launch(c, b->d_out, reinterpret_cast<const DevStep *>(b->d_flt + at), (uint32_t)R.tab[c].size(),
-                                             (uint32_t)R.tiles[c], c == 2 ? d_rows : d_scratch, d_rows + (size_t)R.rows * xlzflt::kDeltaMaxDist,
-                                             (uint32_t)R.groups, stream);
-            if (k < 0) {
-                if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the filter kernels failed\n");
-                (void)hipStreamSynchronize(stream);
-                return XLZ_ERR_DEVICE;
-            }
-            launches += (uint32_t)k;
-            at += R.tab[c].size() * sizeof(DevStep);
-        }
-    }
-    HIP_TRY(hipEventRecord(b->flt_ev1, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, b->flt_ev0, b->flt_ev1));
+    st = timed_bracket(stream, b->flt, "filter kernels", &ms, [&] {
+        at = 0;
+        for (const Round &R : rounds) {
+            uint8_t *d_rows = d_scratch + align_up((size_t)R.windows * 2, 256);
+            for (int c = 0; c < 3; c++) {
+                if (R.tab[c].empty()) continue;
+                const int k = xlz::filter_launch(c, b->d_out, reinterpret_cast<const DevStep *>(b->flt.dev + at), (uint32_t)R.tab[c].size(),
+                                                 (uint32_t)R.tiles[c], c == 2 ? d_rows : d_scratch,
+                                                 d_rows + (size_t)R.rows * xlzflt::kDeltaMaxDist, (uint32_t)R.groups, stream);
+                if (k < 0) return false;
+                launches += (uint32_t)k;
+                at += R.tab[c].size() * sizeof(DevStep);
+            }
+        }
+        return true;
+    });
+    if (st != XLZ_OK) return st;
     acc.device_steps += dev_steps, acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches += launches;
     return XLZ_OK;
 }
@@ -2284,18 +2256,13 @@ extern "C" int xlz_filter_host(uint32_t id, uint32_t param, uint8_t *buf, size_t
 
 extern "C" int xlz_batch_filter(xlz_batch *b, const xlz_filter_step *steps, size_t n)
 {
-    if (!b || !b->ran) return XLZ_ERR_BAD_ARG;
-    int st = filter_args(steps, n, b->n);
+    hipStream_t stream;
+    int st = batch_post_begin(b, [&](size_t streams) { return filter_args(steps, n, streams); }, &stream);
     if (st != XLZ_OK) return st;
-    st = collect(b);
-    if (st != XLZ_OK) return st;
-    xlz_filter_stats acc;
-    memset(&acc, 0, sizeof acc);
-    st = batch_filter_run(b, steps, nullptr, n, 0, b->run_stream ? b->run_stream : b->ctx->stream, acc);
-    if (st != XLZ_OK) return st;
-    std::lock_guard<std::mutex> lock(b->ctx->mu);
-    b->ctx->last_filter = acc;
-    return XLZ_OK;
+    xlz_filter_stats acc = {};
+    st = batch_filter_run(b, steps, nullptr, n, 0, stream, acc);
+    if (st == XLZ_OK) publish(b->ctx, &xlz_ctx::last_filter, acc, false);
+    return st;
 }
 
 extern "C" int xlz_ctx_set_filter_mode(xlz_ctx *ctx, int mode)
@@ -2307,19 +2274,9 @@ extern "C" int xlz_ctx_set_filter_mode(xlz_ctx *ctx, int mode)
 }
 extern "C" int xlz_ctx_filter_mode(const xlz_ctx *ctx) { return ctx ? ctx->filter_mode : XLZ_ERR_BAD_ARG; }
 
-extern "C" int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out)
-{
-    if (!ctx || !out) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    *out = ctx->last_filter;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out) { return last_stats(ctx, &xlz_ctx::last_filter, out); }
 
-void xlz_internal_filter_stats_reset(xlz_ctx *ctx)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    memset(&ctx->last_filter, 0, sizeof ctx->last_filter);
-}
+void xlz_internal_filter_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_filter, xlz_filter_stats{}, false); }
 
 namespace {
 
@@ -2698,31 +2655,139 @@ extern "C" int xlz_decode_batch_plan(const xlz_stream_desc *streams, size_t n, s
     return max_cuts && c.size() > max_cuts ? XLZ_ERR_OUT_CAP : XLZ_OK;
 }
 
-// xlz_decode_batch (n_steps == 0, n_ranges == 0), xlz_decode_batch_checked (n_steps == 0) and xlz_decode_batch_filtered:
-// the filter steps of every (sub-)batch run on the device behind its results and BEFORE it is published as decoded (the
-// downloader starts then, and the filters write); the digests of `ranges` are computed behind them, while the arenas are
-// still the call's.  A sub-batch that has steps never runs sliced: a sliced call ships every slice's bytes while the next
-// slice decodes, before any filter could see them (per-slice filtering with carried state is later work).
-static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const xlz_filter_step *steps,
-                             size_t n_steps, const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, bool accumulate,
-                             xlz_digest *xd = nullptr)
+namespace {
+
+// XLZ_ERR_BAD_ARG for work that the library does not run behind these n streams
+int post_args(const PostWork &w, const xlz_stream_desc *streams, size_t n)
+{
+    const void *out = w.digest_out ? (const void *)w.digest_out : (const void *)w.crc_out;
+    if (check_args(w.ranges, w.n_ranges, n, out, w.digest_out != nullptr) != XLZ_OK || filter_args(w.steps, w.n_steps, n) != XLZ_OK)
+        return XLZ_ERR_BAD_ARG;
+    for (size_t q = 0; q < w.n_steps; q++)
+        if (streams[w.steps[q].stream].flags & XLZ_STREAM_F_LZMA2_SLICE) return XLZ_ERR_BAD_ARG; // (a filter needs the stream's start)
+    return XLZ_OK;
+}
+
+// What a call of xlz_decode_batch runs behind its (sub-)batches, cut at `cuts`.  The pipeline in decode_batch_impl does not
+// care what that is.  It asks must_not_slice(k) when it plans sub-batch k: a sub-batch that has steps never runs sliced,
+// for a sliced call ships every slice's bytes while the next slice decodes, before any filter could see them (per-slice
+// filtering with carried state is later work).  It calls after_collect(k) when k's results are on the host and BEFORE k
+// is published as decoded -- the downloader starts then, and the filters write --, after_publish(k) behind that, while
+// the arena is still the call's -- the digests only read it, so the downloader may go on; they are on the host when it
+// returns, long before the sub-batch is destroyed --, and finish() when every byte of the call is in the callers' buffers.
+struct PostStage {
+    const PostWork &w;
+    xlz_ctx *ctx;
+    const xlz_stream_desc *streams;
+    const std::vector<size_t> &cuts;
+    std::vector<std::vector<size_t>> sub_steps, sub_ranges; // of every sub-batch, in array order
+    // digest_out: the CRCs go through a table of this call and are put into digest_out[] at the end; the SHA-256 ranges
+    // run behind the CRC ranges of their sub-batch, those the host hashes when the call's bytes are in place
+    std::vector<uint64_t> crc_of;
+    uint64_t *crc;
+    std::vector<ShaHostJob> sha_later;
+    xlz_filter_stats flt = {};
+    xlz_check_stats chk = {};
+    xlz_sha256_stats sha = {};
+
+    PostStage(const PostWork &w_, xlz_ctx *ctx_, const xlz_stream_desc *streams_, const std::vector<size_t> &cuts_)
+        : w(w_), ctx(ctx_), streams(streams_), cuts(cuts_), sub_steps(w_.n_steps ? cuts_.size() - 1 : 0),
+          sub_ranges(w_.n_ranges ? cuts_.size() - 1 : 0), crc_of(w_.digest_out ? w_.n_ranges : 0), crc(w_.digest_out ? crc_of.data() : w_.crc_out)
+    {
+        auto sub_of = [&](uint64_t stream) { return (size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)stream) - cuts.begin()) - 1; };
+        for (size_t q = 0; q < w.n_steps; q++) sub_steps[sub_of(w.steps[q].stream)].push_back(q);
+        for (size_t q = 0; q < w.n_ranges; q++) sub_ranges[sub_of(w.ranges[q].stream)].push_back(q);
+    }
+    // The stream the stage's kernels run on -- one of the context's own, not the sub-batch's: in the forms that queue the
+    // next piece's launches before this piece's results are read, a check on the same stream would wait for that piece's
+    // decode (collect() has waited for all that writes the bytes).  The filters use it for the same reason, and the checks
+    // follow them on it.
+    int open()
+    {
+        if (!w.n_ranges && !w.n_steps) return XLZ_OK;
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        if (hipSetDevice(ctx->device) != hipSuccess ||
+            (!ctx->check_stream && hipStreamCreateWithFlags(&ctx->check_stream, hipStreamNonBlocking) != hipSuccess))
+            return XLZ_ERR_DEVICE;
+        return XLZ_OK;
+    }
+    bool must_not_slice(size_t k) const { return w.n_steps && !sub_steps[k].empty(); }
+    bool has_ranges(size_t k) const { return w.n_ranges && !sub_ranges[k].empty(); }
+    // for a k that must_not_slice (xlz_batch_results has run collect() and its re-runs, which write bytes again; nobody
+    // reads the arena yet)
+    int after_collect(size_t k, xlz_batch *b)
+    {
+        return batch_filter_run(b, w.steps, sub_steps[k].data(), sub_steps[k].size(), cuts[k], ctx->check_stream, flt);
+    }
+    int after_publish(size_t k, xlz_batch *b) // for a k that has_ranges
+    {
+        const std::vector<size_t> &idx = sub_ranges[k];
+        int e = batch_checks_run(b, w.ranges, idx.data(), idx.size(), cuts[k], crc, ctx->check_stream, streams + cuts[k], chk);
+        if (e == XLZ_OK && w.digest_out) // (it looks for the XLZ_CHECK_SHA256 ranges among them)
+            e = batch_sha256_run(b, w.ranges, idx.data(), idx.size(), cuts[k], w.digest_out, ctx->check_stream, streams + cuts[k], &sha_later, sha);
+        return e;
+    }
+    // `big`: the streams of 4 GiB and more (sorted), which no batch held: their sessions have written the callers' buffers.
+    // They are settled there, the filters first and in array order, then the checks; the statistics become the context's.
+    // A call without steps does not touch the filters' statistics, one without ranges not the checks', and only the digest
+    // form writes SHA-256's.
+    void finish(int st, const std::vector<size_t> &big, const xlz_result *results)
+    {
+        if (st != XLZ_OK) return;
+        auto is_big = [&](uint64_t stream) { return std::binary_search(big.begin(), big.end(), (size_t)stream); };
+        auto settled = [&](uint64_t stream, uint64_t off, uint64_t len) {
+            return xlzpost::clip({results[stream].out_len, streams[stream].out_cap, false, true, 0}, off, len);
+        };
+        if (w.n_steps) {
+            for (size_t q = 0; q < w.n_steps && !big.empty(); q++) {
+                const xlz_filter_step &f = w.steps[q];
+                if (!is_big(f.stream)) continue;
+                const uint64_t produced = settled(f.stream, 0, xlzpost::kWholeStream).hi;
+                if (produced)
+                    xlzflt::host_apply(f.id, f.param, streams[f.stream].out, produced), flt.host_steps++, flt.host_bytes += produced;
+                else
+                    flt.empty_steps++;
+            }
+            publish(ctx, &xlz_ctx::last_filter, flt, w.accumulate);
+        }
+        if (!w.n_ranges) return;
+        for (size_t q = 0; q < w.n_ranges && !big.empty(); q++) {
+            const xlz_check_range &r = w.ranges[q];
+            if (!is_big(r.stream)) continue;
+            const xlzpost::Clip c = settled(r.stream, r.off, r.len);
+            const uint8_t *p = streams[r.stream].out + c.lo;
+            const uint64_t len = c.hi - c.lo;
+            if (r.kind == XLZ_CHECK_SHA256) {
+                if (len)
+                    sha_later.push_back(ShaHostJob{p, len, &w.digest_out[q]}), sha.host_ranges++, sha.host_bytes += len;
+                else
+                    sha256_of_nothing(&w.digest_out[q]), sha.empty_ranges++;
+                continue;
+            }
+            crc[q] = len ? host_digest(r.kind, p, len) : 0;
+            if (len)
+                chk.host_ranges++, chk.host_bytes += len;
+            else
+                chk.empty_ranges++;
+        }
+        sha256_host_jobs(sha_later);
+        for (size_t q = 0; q < w.n_ranges && w.digest_out; q++)
+            if (w.ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &w.digest_out[q]);
+        xlzpost::stats_add(chk, sha); // (the SHA-256 ranges count in xlz_check_stats too)
+        if (w.digest_out) publish(ctx, &xlz_ctx::last_sha, sha, w.accumulate, xlzpost::ThresholdIsMax{});
+        publish(ctx, &xlz_ctx::last_check, chk, w.accumulate);
+    }
+};
+
+} // namespace
+
+// xlz_decode_batch and, with `post`, xlz_decode_batch_checked, _filtered and _digests
+static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post_work)
 {
     if (!ctx || (!streams && n) || (!results && n)) return XLZ_ERR_BAD_ARG;
     for (size_t i = 0; i < n; i++)
         if (!streams[i].out && streams[i].out_cap) return XLZ_ERR_BAD_ARG;
-    if (check_args(ranges, n_ranges, n, xd ? (const void *)xd : (const void *)digests, xd != nullptr) != XLZ_OK) return XLZ_ERR_BAD_ARG;
-    // xd (xlz_decode_batch_digests): the CRCs go through a table of this call and are put into xd[] at the end; the SHA-256
-    // ranges run behind the CRC ranges of their sub-batch, those the host hashes when the call's bytes are in place
-    std::vector<uint64_t> crc_of(xd ? n_ranges : 0);
-    if (xd) digests = crc_of.data();
-    bool has_sha = false;
-    for (size_t q = 0; q < n_ranges && xd; q++) has_sha |= ranges[q].kind == XLZ_CHECK_SHA256;
-    std::vector<ShaHostJob> sha_later;
-    xlz_sha256_stats sha;
-    memset(&sha, 0, sizeof sha);
-    if (filter_args(steps, n_steps, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
-    for (size_t q = 0; q < n_steps; q++)
-        if (streams[steps[q].stream].flags & XLZ_STREAM_F_LZMA2_SLICE) return XLZ_ERR_BAD_ARG; // (a filter needs the stream's start)
+    if (post_args(post_work, streams, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
     // upload (pinned image, one copy) -> decode -> download (pinned ring, D2H overlapped with the scatter into the
     // callers' buffers).  A call of several wave rounds runs as a PIPELINE of sub-batches on three host threads:
     // sub-batch k+1 is parsed, packed and uploaded and sub-batch k-1 is downloaded and scattered while sub-batch k
@@ -2749,36 +2814,18 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
         std::lock_guard<std::mutex> lock(ctx->mu); // (once: the launching thread holds this lock most of the call)
         sliced_call_bytes = ctx->sliced_call_bytes, slice_bytes = ctx->slice_bytes, max_slices = ctx->max_slices;
     }
-    // filtered calls: the steps of every sub-batch (in array order)
-    std::vector<std::vector<size_t>> sub_steps(n_steps ? S : 0);
-    for (size_t q = 0; q < n_steps; q++)
-        sub_steps[(size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)steps[q].stream) - cuts.begin()) - 1].push_back(q);
-    xlz_filter_stats flt;
-    memset(&flt, 0, sizeof flt);
+    PostStage post(post_work, ctx, streams, cuts);
+    if (post.open() != XLZ_OK) return XLZ_ERR_DEVICE;
     auto slices_for = [&](size_t k) -> uint32_t {
         // (in a pipeline the pieces overlap each other; slices of the first or last piece were measured there: the next
         //  piece's workgroups take the slots every slice boundary frees and the two pieces finish together)
         if (S > 1 && !rounds_mode) return 1;
-        if (n_steps && !sub_steps[k].empty()) return 1; // (a filter must see the bytes before they leave: see above)
+        if (post.must_not_slice(k)) return 1;
         uint64_t total = 0;
         for (size_t i = cuts[k]; i < cuts[k + 1]; i++) total += streams[i].out_cap;
         return total >= sliced_call_bytes ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_slices, total / slice_bytes)) : 1u;
     };
 
-    // checked calls: the ranges of every sub-batch, and the stream their kernels run on -- one of the context's own, not
-    // the sub-batch's: in the forms that queue the next piece's launches before this piece's results are read, a check
-    // on the same stream would wait for that piece's decode (collect() has waited for all that writes the bytes)
-    std::vector<std::vector<size_t>> sub_ranges(n_ranges ? S : 0);
-    xlz_check_stats chk;
-    memset(&chk, 0, sizeof chk);
-    if (n_ranges || n_steps) {
-        for (size_t q = 0; q < n_ranges; q++)
-            sub_ranges[(size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)ranges[q].stream) - cuts.begin()) - 1].push_back(q);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        if (hipSetDevice(ctx->device) != hipSuccess ||
-            (!ctx->check_stream && hipStreamCreateWithFlags(&ctx->check_stream, hipStreamNonBlocking) != hipSuccess))
-            return XLZ_ERR_DEVICE;
-    }
 
     std::vector<xlz_batch *> sub(S, nullptr);
     std::mutex mu;
@@ -2829,10 +2876,8 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
                 for (const UnitResult &u : sub[k]->unit_results) clock.add(u);
         }
         if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu decoded at %.1f ms\n", k, now_ms());
-        // (xlz_batch_results has run collect() and its re-runs, which write bytes again; nobody reads the arena yet.  On the
-        //  check stream for the reason given above; the checks follow on the same stream)
-        if (e == XLZ_OK && n_steps && !sub_steps[k].empty()) {
-            e = batch_filter_run(sub[k], steps, sub_steps[k].data(), sub_steps[k].size(), cuts[k], ctx->check_stream, flt);
+        if (e == XLZ_OK && post.must_not_slice(k)) {
+            e = post.after_collect(k, sub[k]);
             if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu filtered at %.1f ms\n", k, now_ms());
         }
         {
@@ -2842,14 +2887,8 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
             t_decoded = now_ms();
         }
         cv.notify_all();
-        // (the downloader may go on: the check only reads the arena.  The digests are on the host when this returns,
-        //  long before the sub-batch is destroyed)
-        if (e == XLZ_OK && n_ranges && !sub_ranges[k].empty()) {
-            e = batch_checks_run(sub[k], ranges, sub_ranges[k].data(), sub_ranges[k].size(), cuts[k], digests, ctx->check_stream,
-                                 streams + cuts[k], chk);
-            if (e == XLZ_OK && has_sha)
-                e = batch_sha256_run(sub[k], ranges, sub_ranges[k].data(), sub_ranges[k].size(), cuts[k], xd, ctx->check_stream,
-                                     streams + cuts[k], &sha_later, sha);
+        if (e == XLZ_OK && post.has_ranges(k)) {
+            e = post.after_publish(k, sub[k]);
             if (dbg) fprintf(stderr, "xlz_decode_batch: sub-batch %zu checked at %.1f ms\n", k, now_ms());
             if (e != XLZ_OK) {
                 {
@@ -3001,70 +3040,19 @@ static int decode_batch_impl(xlz_ctx *ctx, const xlz_stream_desc *streams, size_
     }
     ctx->pool.end_of_call();
     if (st == XLZ_OK && !big.empty()) st = decode_oversize(ctx, streams, results, big);
-    if (st == XLZ_OK && n_steps) {
-        for (size_t q = 0; q < n_steps && !big.empty(); q++) { // streams of 4 GiB and more: over the caller's buffer, in array order
-            const xlz_filter_step &f = steps[q];
-            if (!std::binary_search(big.begin(), big.end(), (size_t)f.stream)) continue;
-            const uint64_t produced = std::min<uint64_t>(results[f.stream].out_len, streams[f.stream].out_cap);
-            if (produced)
-                xlzflt::host_apply(f.id, f.param, streams[f.stream].out, produced), flt.host_steps++, flt.host_bytes += produced;
-            else
-                flt.empty_steps++;
-        }
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        if (accumulate)
-            filter_stats_add(ctx->last_filter, flt);
-        else
-            ctx->last_filter = flt;
-    }
-    if (st == XLZ_OK && n_ranges) {
-        for (size_t q = 0; q < n_ranges && !big.empty(); q++) { // streams of 4 GiB and more: over the caller's buffer
-            const xlz_check_range &r = ranges[q];
-            if (!std::binary_search(big.begin(), big.end(), (size_t)r.stream)) continue;
-            const uint64_t produced = std::min<uint64_t>(results[r.stream].out_len, streams[r.stream].out_cap);
-            const uint64_t lo = std::min(r.off, produced), hi = r.len > produced - lo ? produced : lo + r.len;
-            if (r.kind == XLZ_CHECK_SHA256) {
-                if (hi > lo)
-                    sha_later.push_back(ShaHostJob{streams[r.stream].out + lo, hi - lo, &xd[q]}), sha.host_ranges++, sha.host_bytes += hi - lo;
-                else
-                    sha256_of_nothing(&xd[q]), sha.empty_ranges++;
-                continue;
-            }
-            digests[q] = hi > lo ? host_digest(r.kind, streams[r.stream].out + lo, hi - lo) : 0;
-            if (hi > lo)
-                chk.host_ranges++, chk.host_bytes += hi - lo;
-            else
-                chk.empty_ranges++;
-        }
-        sha256_host_jobs(sha_later); // (every byte of the call is in the callers' buffers)
-        for (size_t q = 0; q < n_ranges && xd; q++)
-            if (ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(digests[q], &xd[q]);
-        check_stats_add_sha(chk, sha);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        if (xd && accumulate)
-            sha_stats_add(ctx->last_sha, sha);
-        else if (xd)
-            ctx->last_sha = sha;
-        if (accumulate) {
-            xlz_check_stats &t = ctx->last_check;
-            t.device_ranges += chk.device_ranges, t.device_bytes += chk.device_bytes, t.host_ranges += chk.host_ranges;
-            t.host_bytes += chk.host_bytes, t.empty_ranges += chk.empty_ranges, t.kernel_ms += chk.kernel_ms, t.launches += chk.launches;
-        } else {
-            ctx->last_check = chk;
-        }
-    }
+    post.finish(st, big, results);
     return st;
 }
 
 extern "C" int xlz_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results)
 {
-    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, nullptr, 0, nullptr, false);
+    return decode_batch_impl(ctx, streams, n, results, PostWork{});
 }
 
 extern "C" int xlz_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
                                         const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests)
 {
-    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, ranges, n_ranges, digests, false);
+    return decode_batch_impl(ctx, streams, n, results, PostWork{nullptr, 0, ranges, n_ranges, digests, nullptr, false});
 }
 
 extern "C" int xlz_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
@@ -3073,35 +3061,19 @@ extern "C" int xlz_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *st
 {
     // (a machine without a HIP device has no context to pass; the filters of such a call are not run on the host instead)
     if (!ctx && xlz_device_count() == 0) return XLZ_ERR_DEVICE;
-    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, digests, false);
-}
-
-int xlz_internal_decode_batch_filtered(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
-                                       const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
-                                       uint64_t *digests, int accumulate)
-{
-    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, digests, accumulate != 0);
+    return decode_batch_impl(ctx, streams, n, results, PostWork{steps, n_steps, ranges, n_ranges, digests, nullptr, false});
 }
 
 extern "C" int xlz_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
                                         const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
                                         xlz_digest *out)
 {
-    if (!ctx) return XLZ_ERR_BAD_ARG;
-    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, nullptr, false, out);
+    return decode_batch_impl(ctx, streams, n, results, PostWork{steps, n_steps, ranges, n_ranges, nullptr, out, false});
 }
 
-int xlz_internal_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
-                                      const xlz_filter_step *steps, size_t n_steps, const xlz_check_range *ranges, size_t n_ranges,
-                                      xlz_digest *out, int accumulate)
+int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post)
 {
-    return decode_batch_impl(ctx, streams, n, results, steps, n_steps, ranges, n_ranges, nullptr, accumulate != 0, out);
-}
-
-int xlz_internal_decode_batch_checked(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results,
-                                      const xlz_check_range *ranges, size_t n_ranges, uint64_t *digests, int accumulate)
-{
-    return decode_batch_impl(ctx, streams, n, results, nullptr, 0, ranges, n_ranges, digests, accumulate != 0);
+    return decode_batch_impl(ctx, streams, n, results, post);
 }
 
 // Multi-GPU form of xlz_decode_batch.  The streams are independent, and so are the units of an

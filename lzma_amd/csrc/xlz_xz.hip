@@ -324,23 +324,21 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         dg.assign(nb, 0);
         xlz_internal_check_stats_reset(ctxs[0]);
         if (chains) xlz_internal_filter_stats_reset(ctxs[0]);
-        if (dev_sha) {
-            std::vector<xlz_digest> xgot(cr.size());
-            xdg.resize(nb);
-            st = xlz_internal_decode_batch_digests(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, cr.data(), cr.size(), xgot.data(), 1);
-            for (size_t k = 0; k < of.size(); k++) {
+        // (mode 2 asks for the 32-byte form only where a block needs it: the SHA-256 statistics are that form's alone)
+        std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0);
+        if (dev_sha) xdg.resize(nb);
+        const PostWork w = {fs.data(), nfs, cr.data(), cr.size(), dev_sha ? nullptr : got.data(), dev_sha ? xgot.data() : nullptr, true};
+        st = xlz_internal_decode_batch(ctxs[0], d.data(), nb, r.data(), w);
+        for (size_t k = 0; k < of.size(); k++) {
+            if (dev_sha) {
                 xdg[of[k]] = xgot[k];
-                for (int j = 0; j < 8; j++) dg[of[k]] |= (uint64_t)xgot[k].b[j] << (8 * j); // (a CRC: little-endian in b[0..7])
+                for (int j = 0; j < 8; j++) got[k] |= (uint64_t)xgot[k].b[j] << (8 * j); // (a CRC: little-endian in b[0..7])
             }
-        } else {
-            st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, cr.data(), cr.size(), got.data(), 1)
-                     : xlz_internal_decode_batch_checked(ctxs[0], d.data(), nb, r.data(), cr.data(), cr.size(), got.data(), 1);
-            for (size_t k = 0; k < of.size(); k++) dg[of[k]] = got[k];
+            dg[of[k]] = got[k];
         }
     } else if (chains) { // (the digests, if any, on host threads below: over the filtered bytes)
         xlz_internal_filter_stats_reset(ctxs[0]);
-        st = nfs ? xlz_internal_decode_batch_filtered(ctxs[0], d.data(), nb, r.data(), fs.data(), nfs, nullptr, 0, nullptr, 1)
-                 : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
+        st = xlz_internal_decode_batch(ctxs[0], d.data(), nb, r.data(), PostWork{fs.data(), nfs, nullptr, 0, nullptr, nullptr, true});
     } else
         st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), nb, r.data()) : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
     if (st != XLZ_OK) return st;
