@@ -407,6 +407,34 @@ typedef struct xlz_sha256_stats {
 } xlz_sha256_stats;
 int xlz_ctx_last_sha256_stats(xlz_ctx *ctx, xlz_sha256_stats *out);
 
+/* ---- pack into device memory (lzma_amd/csrc/xlz_pack_dev.hip) -------
+ * The output arena keeps every stream in a region of its own, so a decoded file is never contiguous in HBM.  The pack
+ * copies ranges of the decoded (and, behind xlz_batch_filter, filtered) outputs of a batch into ONE caller-owned device
+ * buffer, on the device: nothing leaves HBM.  Like xlz_batch_checks it waits for and collects the batch's latest run.
+ * An item is clipped to what its stream produced, as a check range is; copied[i] (copied may be NULL) = the bytes written
+ * for item i, 0 for a stream that never sat in the arena.  Bytes of the destination that no item covers are not written.
+ * The call returns when its stream has drained; no other stream may use d_dst meanwhile.  XLZ_ERR_BAD_ARG: NULL
+ * arguments with n > 0; a stream index >= the batch's streams; d_dst is not device memory of the context's device, or
+ * dst_cap reaches past its allocation; an item's [dst_off, dst_off + len) does not fit in dst_cap (or the sum
+ * overflows); the declared destination ranges of two items overlap.  Nothing is written then.                    */
+typedef struct xlz_pack_item {
+    uint64_t stream;   /* index into the batch's streams                                                     */
+    uint64_t off, len; /* bytes of THAT STREAM'S OUTPUT, clipped to what it produced                         */
+    uint64_t dst_off;  /* where they go in the destination                                                   */
+} xlz_pack_item;
+int xlz_batch_pack(xlz_batch *batch, const xlz_pack_item *items, size_t n, void *d_dst, size_t dst_cap, uint64_t *copied);
+/* Of the most recent xlz_batch_pack on `ctx`, or of the pack of the most recent xlz_xz_decode_device /
+ * xlz_7z_decode_device.                                                                                           */
+typedef struct xlz_pack_stats {
+    uint64_t items, bytes;    /* what the kernel copied                                                      */
+    uint64_t congruent_items; /* ... of them: source and destination addresses congruent modulo 16 (one load per store) */
+    uint64_t empty_items;     /* clipped to nothing: they never reach the kernel                             */
+    double kernel_ms;         /* the kernel by HIP events                                                    */
+    uint32_t launches;
+    uint32_t reserved;
+} xlz_pack_stats;
+int xlz_ctx_last_pack_stats(xlz_ctx *ctx, xlz_pack_stats *out);
+
 /* ---- pull-style readers mirroring the reference's Go surface --------------- */
 /* Constructors take the compressed stream as a buffer (a Go shim slurps its io.Reader
  * first) and copy it.  Constructor-time errors are the ones the reference's
@@ -560,6 +588,17 @@ int xlz_xz_index_chains(const uint8_t *file, size_t len, xlz_xz_block *blocks, s
  * XLZ_ERR_RESULT.                                                                             */
 int xlz_xz_decode(xlz_ctx *ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
                   uint64_t *out_len, int verify, size_t *unverified);
+/* xlz_xz_decode into DEVICE memory: d_out is out_cap bytes on the context's device, and the decoded file ends up
+ * there contiguous -- decode, filters (filter mode 1, as xlz_xz_decode), checks and a pack (xlz_batch_pack) all run on the
+ * device; only the digests come to the host, where they are compared.  Same status, *out_len and *unverified as
+ * xlz_xz_decode on the same context for every input, with one exception: a block of 4 GiB or more is
+ * XLZ_ERR_UNSUPPORTED.  verify != 0 always checks through the check kernels (CRC32 / CRC64) and the xlz_batch_digests
+ * path (SHA-256), whatever the context's check mode: that mode says where a host-destination call verifies.  On failure
+ * *out_len = 0 and the contents of d_out are unspecified.  The call holds the output arena AND the destination: about
+ * twice the decoded size of device memory.  It returns when its work on the device is done; no other stream may use
+ * d_out meanwhile.                                                                                                 */
+int xlz_xz_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_out, size_t out_cap,
+                         uint64_t *out_len, int verify, size_t *unverified);
 /* the same over several contexts (one per GPU): the blocks -- and the units inside large blocks -- are
  * dealt to the contexts by xlz_decode_batch_multi                                                */
 int xlz_xz_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out,
@@ -621,6 +660,11 @@ int xlz_7z_index_chains(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_fo
  * when a folder is not a single LZMA / LZMA2 / Copy coder (filter mode 1: nor a chain as above).   */
 int xlz_7z_decode(xlz_ctx *ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
                   uint64_t *out_len, int verify, size_t *unverified);
+/* xlz_7z_decode into DEVICE memory, as xlz_xz_decode_device: same status, *out_len and *unverified as xlz_7z_decode,
+ * except that a folder of 4 GiB or more is XLZ_ERR_UNSUPPORTED.  A Copy folder is uploaded from the file; its CRC is
+ * computed on the host over the file's bytes.  About twice the decoded size of device memory.                     */
+int xlz_7z_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_out, size_t out_cap,
+                         uint64_t *out_len, int verify, size_t *unverified);
 /* the same over several contexts (one per GPU; encoded headers are decoded on the first)         */
 int xlz_7z_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out,
                         size_t out_cap, uint64_t *out_len, int verify, size_t *unverified);

@@ -154,6 +154,15 @@ class Context:
             raise LzmaError(st, "xlz_ctx_last_filter_stats")
         return {k: getattr(fs, k) for k, _ in N.FilterStats._fields_ if k != "reserved"}
 
+    def last_pack_stats(self):
+        """what the pack kernel copied in the last Batch.pack / xz_decode_device / sevenzip_decode_device on this context
+        (xlz_ctx_last_pack_stats) -> dict"""
+        ps = N.PackStats()
+        st = N.lib().xlz_ctx_last_pack_stats(self._h, ctypes.byref(ps))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_pack_stats")
+        return {k: getattr(ps, k) for k, _ in N.PackStats._fields_ if k != "reserved"}
+
     def event_record(self, slot):
         st = N.lib().xlz_ctx_event_record(self._h, slot)
         if st != OK:
@@ -499,6 +508,21 @@ class Batch:
         st = N.lib().xlz_batch_filter(self._h, _make_steps(steps), len(steps))
         if st != OK:
             raise LzmaError(st, "xlz_batch_filter")
+
+    def pack(self, items, dptr, cap):
+        """copy ranges of the decoded (and filtered) outputs into one device buffer, on the device (xlz_batch_pack).
+        items: [(stream index, off, len, dst_off), ...], clipped to what each stream produced; dptr / cap: device memory of
+        the context's device, as an integer address and its size -> the bytes copied per item"""
+        items = list(items)
+        n = len(items)
+        arr = (N.PackItem * max(n, 1))()
+        for q, (stream, off, length, dst_off) in enumerate(items):
+            arr[q].stream, arr[q].off, arr[q].len, arr[q].dst_off = int(stream), int(off), int(length), int(dst_off)
+        copied = (ctypes.c_uint64 * max(n, 1))()
+        st = N.lib().xlz_batch_pack(self._h, arr, n, ctypes.c_void_p(int(dptr)), int(cap), copied)
+        if st != OK:
+            raise LzmaError(st, "xlz_batch_pack")
+        return list(copied[:n])
 
     def download(self, i, length):
         buf = ctypes.create_string_buffer(max(int(length), 1))
@@ -898,3 +922,54 @@ def sevenzip_decode(ctx, data, verify=True, max_size=None):
     if st != OK:
         raise LzmaError(st, "xlz_7z_decode")
     return out.raw[: out_len.value]
+
+
+# ---- the container front-ends into device memory (include/xlz.h: xlz_xz_decode_device / xlz_7z_decode_device) ----
+def _decode_device(name, ctx, data, dptr, cap, verify):
+    if not isinstance(data, bytes):
+        data = bytes(data)
+    out_len, unverified = ctypes.c_uint64(), ctypes.c_size_t()
+    st = getattr(N.lib(), name)(ctx._h, ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p), len(data), ctypes.c_void_p(int(dptr)),
+                                int(cap), ctypes.byref(out_len), 1 if verify else 0, ctypes.byref(unverified))
+    if st != OK:
+        raise LzmaError(st, name)
+    return out_len.value
+
+
+def xz_decode_device(ctx, data, dptr, cap, verify=True):
+    """xlz_xz_decode_device: decode a whole .xz file into `cap` bytes of device memory at the address `dptr` (on the
+    context's device), contiguous; decode, filters, checks and the pack run on the device -> number of bytes decoded.
+    Raises LzmaError as xz_decode does.  The call needs about twice the decoded size of device memory."""
+    return _decode_device("xlz_xz_decode_device", ctx, data, dptr, cap, verify)
+
+
+def sevenzip_decode_device(ctx, data, dptr, cap, verify=True):
+    """xlz_7z_decode_device: the same for a .7z archive -> number of bytes decoded (the files back to back)"""
+    return _decode_device("xlz_7z_decode_device", ctx, data, dptr, cap, verify)
+
+
+def _decode_tensor(decode, total, ctx, data, verify, out):
+    import torch  # (only here: importing lzma_amd does not import torch)
+    dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
+    if out is None:
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
+        raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
+    elif out.numel() < total:
+        raise LzmaError(ERR_OUT_CAP, "the index announces %d bytes, out holds %d" % (total, out.numel()))
+    torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
+    n = decode(ctx, data, out.data_ptr(), out.numel(), verify=verify)
+    return out[:n]
+
+
+def xz_decode_tensor(ctx, data, verify=True, out=None):
+    """xz_decode_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least the
+    index's total; ERR_OUT_CAP if smaller) or a new one -> the tensor cut to the decoded size"""
+    total = xz_index_chains(data)[2] if ctx.filter_mode() == 1 else xz_index(data)[1]
+    return _decode_tensor(xz_decode_device, total, ctx, data, verify, out)
+
+
+def sevenzip_decode_tensor(ctx, data, verify=True, out=None):
+    """sevenzip_decode_device into a torch.uint8 tensor on the context's device, as xz_decode_tensor"""
+    total = sevenzip_index_chains(data, ctx)[3] if ctx.filter_mode() == 1 else sevenzip_index(data, ctx)[2]
+    return _decode_tensor(sevenzip_decode_device, total, ctx, data, verify, out)

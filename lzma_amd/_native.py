@@ -56,6 +56,7 @@ EXPORTS = [
     "xlz_filter_host", "xlz_batch_filter", "xlz_decode_batch_filtered", "xlz_ctx_set_filter_mode", "xlz_ctx_filter_mode",
     "xlz_ctx_last_filter_stats", "xlz_xz_index_chains", "xlz_7z_index_chains",
     "xlz_batch_digests", "xlz_decode_batch_digests", "xlz_sha256_plan", "xlz_ctx_last_sha256_stats",
+    "xlz_batch_pack", "xlz_ctx_last_pack_stats", "xlz_xz_decode_device", "xlz_7z_decode_device",
 ]
 
 
@@ -119,6 +120,16 @@ class FilterStats(ctypes.Structure):
     _fields_ = [("device_steps", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_steps", ctypes.c_uint64),
                 ("host_bytes", ctypes.c_uint64), ("empty_steps", ctypes.c_uint64), ("kernel_ms", ctypes.c_double),
                 ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PackItem(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint64), ("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64)]
+
+
+class PackStats(ctypes.Structure):
+    _fields_ = [("items", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("congruent_items", ctypes.c_uint64),
+                ("empty_items", ctypes.c_uint64), ("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 class XzBlock(ctypes.Structure):
@@ -309,6 +320,11 @@ def lib():
         L.xlz_sha256_plan.argtypes = [ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_uint32, ctypes.c_double, ctypes.c_double,
                                       ctypes.POINTER(ctypes.c_uint8)]
         L.xlz_ctx_last_sha256_stats.argtypes = [vp, ctypes.POINTER(Sha256Stats)]
+    if hasattr(L, "xlz_batch_pack"):  # (an older library loaded through XLZ_SO has no pack into device memory)
+        L.xlz_batch_pack.argtypes = [vp, ctypes.POINTER(PackItem), sz, vp, sz, ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_ctx_last_pack_stats.argtypes = [vp, ctypes.POINTER(PackStats)]
+        L.xlz_xz_decode_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
+        L.xlz_7z_decode_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
     _lib = L
     return L
 

@@ -437,9 +437,12 @@ int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> 
 int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_folder> &fo,
                    const std::vector<xlz_7z_substream> &subs, uint8_t *out, int verify, size_t *unverified,
                    xlz_ctx *const *ctxs = nullptr, size_t n_ctx = 0, // ctxs: deal the folders to several GPUs (xlz_decode_batch_multi)
-                   const std::vector<Folder> *chains = nullptr)      // filter mode 1: the folders' filter steps (Folder::steps)
+                   const std::vector<Folder> *chains = nullptr,      // filter mode 1: the folders' filter steps (Folder::steps)
+                   void *d_out = nullptr, size_t d_cap = 0)          // the device-destination form (xlz_7z_decode_device; out == NULL)
 {
     std::vector<xlz_filter_step> fs;
+    std::vector<DeviceCopy> copies; // d_out: the Copy folders go up from the file as they are
+    std::vector<uint64_t> want_out, dst_off;
     std::vector<xlz_stream_desc> d;
     std::vector<size_t> which;
     uint8_t propbuf[5];
@@ -449,14 +452,17 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
         if (f.method == XLZ_7Z_UNSUPPORTED) return XLZ_ERR_UNSUPPORTED;
         if (f.method == XLZ_7Z_COPY) {
             if (f.pack_len != f.unpack_len) return XLZ_ERR_RESULT;
-            memcpy(out + f.unpack_off, file + f.pack_off, (size_t)f.unpack_len);
+            if (d_out)
+                copies.push_back(DeviceCopy{f.unpack_off, file + f.pack_off, f.unpack_len});
+            else
+                memcpy(out + f.unpack_off, file + f.pack_off, (size_t)f.unpack_len);
             continue;
         }
         xlz_stream_desc s;
         memset(&s, 0, sizeof s);
         s.in = file + f.pack_off;
         s.in_len = (size_t)f.pack_len;
-        s.out = out + f.unpack_off;
+        s.out = d_out ? nullptr : out + f.unpack_off;
         s.out_cap = (size_t)f.unpack_len;
         if (f.method == XLZ_7Z_LZMA) { // NewLZMADecompressorForSevenZip(props, unpackSize, readers), reader1.go:32-61
             s.format = XLZ_FMT_LZMA_RAW;
@@ -476,12 +482,21 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
             }
         d.push_back(s);
         which.push_back(i);
+        want_out.push_back(f.unpack_len), dst_off.push_back(f.unpack_off);
     }
     std::vector<xlz_result> r(d.size());
+    DeviceDest dest;
+    dest.d_dst = d_out, dest.cap = d_cap, dest.want_out = want_out.data(), dest.dst_off = dst_off.data();
+    dest.copies = copies.data(), dest.n_copies = copies.size();
+    // (a device destination: one batch with what `w` asks for behind it, the pack and the Copy folders' upload)
+    auto decode = [&](const PostWork &w) {
+        return d_out ? xlz_internal_decode_device(ctx, d.data(), d.size(), r.data(), w, dest) : xlz_internal_decode_batch(ctx, d.data(), d.size(), r.data(), w);
+    };
     // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 of every file and folder that the batch decodes comes
     // from the device with the batch's results -- per-file ranges inside solid folders --, in the order the loop below
     // asks for them: dg[dg_first[i] ...] = folder i's files that carry a CRC, then the folder's own
-    const bool dev = verify && n_ctx <= 1 && ctx && xlz_ctx_check_mode(ctx) >= 1;
+    // (a device destination: there are no bytes on the host to check, so always)
+    const bool dev = verify && n_ctx <= 1 && ctx && (d_out || xlz_ctx_check_mode(ctx) >= 1);
     std::vector<uint64_t> dg;
     std::vector<size_t> dg_first(fo.size(), 0);
     if (dev) {
@@ -507,13 +522,12 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
             }
         }
         dg.resize(cr.size());
-        if (!d.empty()) {
-            int st = xlz_internal_decode_batch(ctx, d.data(), d.size(), r.data(),
-                                               PostWork{fs.data(), fs.size(), cr.data(), cr.size(), dg.data(), nullptr, true});
+        if (!d.empty() || d_out) {
+            int st = decode(PostWork{fs.data(), fs.size(), cr.data(), cr.size(), dg.data(), nullptr, true});
             if (st != XLZ_OK) return st;
         }
-    } else if (!fs.empty()) { // (CRCs, if asked for, on host threads below: over the filtered bytes)
-        int st = xlz_internal_decode_batch(ctx, d.data(), d.size(), r.data(), PostWork{fs.data(), fs.size(), nullptr, 0, nullptr, nullptr, true});
+    } else if (!fs.empty() || d_out) { // (CRCs, if asked for, on host threads below: over the filtered bytes)
+        int st = decode(PostWork{fs.data(), fs.size(), nullptr, 0, nullptr, nullptr, true});
         if (st != XLZ_OK) return st;
     } else if (!d.empty()) {
         int st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), d.size(), r.data())
@@ -532,7 +546,10 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
         auto work = [&](unsigned t) {
             for (size_t i = t; i < fo.size(); i += nth) {
                 const xlz_7z_folder &f = fo[i];
-                uint64_t o = f.unpack_off;
+                // what the host reads of the folder: its bytes in the caller's buffer, or (a device destination, where only
+                // Copy folders are the host's) in the file
+                const uint8_t *fb = d_out ? file + f.pack_off : out + f.unpack_off;
+                uint64_t o = 0;
                 bool any = false;
                 const bool on_dev = dev && f.method != XLZ_7Z_COPY; // (Copy folders never were on the device)
                 size_t q = dg_first[i];
@@ -540,13 +557,13 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
                     const xlz_7z_substream &ss = subs[f.first_substream + k];
                     if (ss.has_crc) {
                         any = true;
-                        if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(out + o, (size_t)ss.size)) != ss.crc) bad[i] = 1;
+                        if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(fb + o, (size_t)ss.size)) != ss.crc) bad[i] = 1;
                     }
                     o += ss.size;
                 }
                 if (f.has_crc) {
                     any = true;
-                    if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(out + f.unpack_off, (size_t)f.unpack_len)) != f.crc) bad[i] = 1;
+                    if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(fb, (size_t)f.unpack_len)) != f.crc) bad[i] = 1;
                 }
                 if (!any && !bad[i]) bad[i] = 2;
             }
@@ -708,7 +725,20 @@ extern "C" int xlz_7z_index_chains(xlz_ctx *ctx, const uint8_t *file, size_t len
 }
 
 static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
-                     uint64_t *out_len, int verify, size_t *unverified);
+                     uint64_t *out_len, int verify, size_t *unverified, void *d_out = nullptr);
+
+// Into device memory: the same parse, batch and comparisons as xlz_7z_decode; the CRCs of what the batch decodes always come
+// from the device (as in check mode 1), Copy folders are uploaded from the file and checked there, and a pack puts the
+// folders side by side in d_out (xlz_internal_decode_device).  An encoded header is decoded into host memory as ever.
+extern "C" int xlz_7z_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_out, size_t out_cap, uint64_t *out_len,
+                                    int verify, size_t *unverified)
+{
+    if (!ctx || (!d_out && out_cap)) return XLZ_ERR_BAD_ARG;
+    uint8_t none = 0; // (an empty archive needs no destination)
+    const int st = sz_decode(&ctx, 1, file, len, nullptr, out_cap, out_len, verify, unverified, d_out ? d_out : &none);
+    if (st != XLZ_OK && out_len) *out_len = 0;
+    return st;
+}
 
 extern "C" int xlz_7z_decode(xlz_ctx *ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap, uint64_t *out_len,
                              int verify, size_t *unverified)
@@ -726,15 +756,15 @@ extern "C" int xlz_7z_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uin
 }
 
 static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
-                     uint64_t *out_len, int verify, size_t *unverified)
+                     uint64_t *out_len, int verify, size_t *unverified, void *d_out)
 {
     for (size_t c = 0; c < n_ctx; c++)
         if (!ctxs[c]) return XLZ_ERR_BAD_ARG;
     xlz_ctx *ctx = ctxs[0];
-    if (!file || (!out && out_cap) || !out_len) return XLZ_ERR_BAD_ARG;
+    if (!file || (!out && out_cap && !d_out) || !out_len) return XLZ_ERR_BAD_ARG;
     *out_len = 0;
     if (unverified) *unverified = 0;
-    if (verify && n_ctx == 1 && xlz_ctx_check_mode(ctx) >= 1) xlz_internal_check_stats_reset(ctx); // (an encoded header's batch counts too)
+    if (verify && n_ctx == 1 && (d_out || xlz_ctx_check_mode(ctx) >= 1)) xlz_internal_check_stats_reset(ctx); // (an encoded header's batch counts too)
     Streams s;
     std::vector<uint8_t> dh;
     int st = main_streams(ctx, file, len, s, dh);
@@ -748,7 +778,7 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     uint64_t total = 0;
     for (auto &f : fo) total += f.unpack_len;
     if (total > out_cap) return XLZ_ERR_OUT_CAP;
-    st = decode_folders(ctx, file, fo, s.subs, out, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr);
+    st = decode_folders(ctx, file, fo, s.subs, out, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr, d_out, out_cap);
     if (st != XLZ_OK) return st;
     *out_len = total;
     return XLZ_OK;

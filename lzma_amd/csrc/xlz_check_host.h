@@ -13,3 +13,25 @@ void xlz_internal_filter_stats_reset(xlz_ctx *ctx);
 void xlz_internal_sha256_stats_reset(xlz_ctx *ctx);
 // xlz_decode_batch with what `post` asks for behind it: xlz_decode_batch_checked, _filtered and _digests are this
 int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post);
+
+// Where xlz_xz_decode_device / xlz_7z_decode_device want the decoded bytes: stream i of the call must produce exactly
+// want_out[i] bytes (and, where want_in is given, use exactly want_in[i] bytes of input), which go to d_dst + dst_off[i];
+// copies: bytes that go there from the host as they are (.7z Copy folders).
+struct DeviceCopy {
+    uint64_t dst_off;
+    const uint8_t *src;
+    uint64_t len;
+};
+struct DeviceDest {
+    void *d_dst = nullptr;
+    size_t cap = 0;
+    const uint64_t *want_out = nullptr, *want_in = nullptr, *dst_off = nullptr;
+    const DeviceCopy *copies = nullptr;
+    size_t n_copies = 0;
+};
+// The device-destination form of xlz_internal_decode_batch (streams[i].out is NULL): one batch -- create, run, results,
+// the size checks above (a stream's own failure, then XLZ_ERR_RESULT), post.steps, post.ranges (exactly one of crc_out /
+// digest_out when there are ranges; the statistics always accumulate), the pack into dest, the copies, and a wait for
+// the context's stream.  XLZ_ERR_UNSUPPORTED for a stream of 4 GiB and more.
+int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
+                               const DeviceDest &dest);

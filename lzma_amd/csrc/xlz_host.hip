@@ -32,6 +32,7 @@
 #include "xlz_check_host.h"
 #include "xlz_sha256_dev.h"
 #include "xlz_filter_dev.h"
+#include "xlz_pack_dev.h"
 
 using namespace xlz;
 
@@ -249,6 +250,7 @@ struct xlz_ctx {
     // filters (xlz_filter_dev.hip): xlz_ctx_set_filter_mode, xlz_ctx_last_filter_stats
     int filter_mode = 0;
     xlz_filter_stats last_filter = {};
+    xlz_pack_stats last_pack = {}; // xlz_ctx_last_pack_stats (xlz_pack_dev.hip)
 };
 
 // Scratch of one kind of post-decode kernel of a batch: device and pinned memory from where the batch's memory comes
@@ -339,8 +341,8 @@ struct xlz_batch {
     PinLease in_lease;
     // the post-decode stage's scratch (PostScratch), one per kind of kernel.  Checks: range table | segment values |
     // digests on the device, range table | digests pinned.  SHA-256: digests | range table on both sides.  Filters: step
-    // tables | window table | rows of sums on the device, the step tables pinned.
-    PostScratch chk, sha, flt;
+    // tables | window table | rows of sums on the device, the step tables pinned.  Pack: the item table on both sides.
+    PostScratch chk, sha, flt, pk;
 };
 
 // ---------------------------------------------------------------- helpers ----
@@ -850,6 +852,7 @@ int batch_free(xlz_batch *b)
     b->chk.release(b);
     b->sha.release(b);
     b->flt.release(b);
+    b->pk.release(b);
     delete b;
     return XLZ_OK;
 }
@@ -2278,6 +2281,114 @@ extern "C" int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out) { 
 
 void xlz_internal_filter_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_filter, xlz_filter_stats{}, false); }
 
+// ---------------------------------------------------------------- pack into device memory ----
+namespace xlz {
+int pack_launch(const uint8_t *arena, uint64_t arena_bytes, uint8_t *dst, const xlzpack::DevItem *items, uint32_t n_items, uint64_t tile0,
+                uint64_t n_tiles, int num_cus, hipStream_t stream);
+}
+
+namespace {
+
+// the pack kernel's out-of-item reads stay inside the arena because of this layout (xlz_pack_dev.h: load16)
+static_assert(xlzpack::kRegionAlign == kArenaAlign && xlzpack::kRegionPad == kOutTailPad, "xlz_pack_dev.h describes another arena");
+
+// [p, p + cap) is device memory of the context's device (as far as the runtime tells: the range of the allocation is
+// looked at where it is known)
+int device_dst_ok(xlz_ctx *ctx, const void *p, size_t cap)
+{
+    if (!p) return XLZ_ERR_BAD_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { // (a pointer the runtime does not know: plain host memory)
+        (void)hipGetLastError();
+        return XLZ_ERR_BAD_ARG;
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return XLZ_ERR_BAD_ARG;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return XLZ_OK;
+    }
+    const uintptr_t lo = (uintptr_t)base, at_p = (uintptr_t)p;
+    return at_p >= lo && at_p - lo <= size && cap <= size - (at_p - lo) ? XLZ_OK : XLZ_ERR_BAD_ARG;
+}
+
+// Packs items[0 .. n) (accepted by xlzpost::pack_items_ok) of a COLLECTED batch into d_dst, by the pack kernel on `stream`
+// -- the batch's own: the kernel runs alone, behind everything that wrote the arena -- and waits for it.  copied
+// (optional) is indexed like items[].  Streams outside the arena contribute nothing.
+int batch_pack_run(xlz_batch *b, const xlz_pack_item *items, size_t n, void *d_dst, uint64_t *copied, hipStream_t stream, xlz_pack_stats &acc)
+{
+    using xlzpack::DevItem;
+    const uint64_t mis = (uintptr_t)d_dst & 15; // the kernel's destination pointer is d_dst rounded down to 16
+    std::vector<DevItem> tab;
+    for (size_t i = 0; i < n; i++) {
+        const size_t s = (size_t)items[i].stream;
+        const xlzpost::Clip c = xlzpost::clip(stream_out(b, s, nullptr), items[i].off, items[i].len);
+        if (copied) copied[i] = 0;
+        if (c.place != xlzpost::Place::Arena) {
+            acc.empty_items++;
+            continue;
+        }
+        DevItem d;
+        d.src = b->plans[s].out_off + c.lo, d.dst = items[i].dst_off + mis, d.len = c.hi - c.lo;
+        if (d.src + d.len > b->out_bytes) return XLZ_ERR_UNSUPPORTED;
+        tab.push_back(d);
+        if (copied) copied[i] = d.len;
+        acc.bytes += d.len, acc.congruent_items += xlzpack::congruent(d);
+    }
+    if (tab.empty()) return XLZ_OK;
+    if (tab.size() > 0xFFFFFFFFull || ((uintptr_t)b->d_out & 15)) return XLZ_ERR_UNSUPPORTED;
+    std::sort(tab.begin(), tab.end(), [](const DevItem &x, const DevItem &y) { return x.dst < y.dst; });
+    xlz_ctx *ctx = b->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t tab_bytes = tab.size() * sizeof(DevItem);
+    int st = b->pk.reserve(b, tab_bytes, tab_bytes);
+    if (st != XLZ_OK) return st;
+    memcpy(b->pk.pin, tab.data(), tab_bytes);
+    const DevItem *d_tab = reinterpret_cast<const DevItem *>(b->pk.dev);
+    HIP_TRY(hipMemcpyAsync(b->pk.dev, b->pk.pin, tab_bytes, hipMemcpyHostToDevice, stream));
+    float ms = 0;
+    st = timed_bracket(stream, b->pk, "pack kernel", &ms, [&] {
+        return xlz::pack_launch(b->d_out, b->out_bytes, static_cast<uint8_t *>(d_dst) - mis, d_tab, (uint32_t)tab.size(),
+                                xlzpack::first_tile(tab.data()), xlzpack::tile_count(tab.data(), (uint32_t)tab.size()), ctx->num_cus,
+                                stream) == 0;
+    });
+    if (st != XLZ_OK) return st;
+    acc.items += tab.size(), acc.kernel_ms += ms, acc.launches++;
+    return XLZ_OK;
+}
+
+void publish_pack(xlz_ctx *ctx, const xlz_pack_stats &v)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_pack = v;
+}
+
+} // namespace
+
+extern "C" int xlz_batch_pack(xlz_batch *b, const xlz_pack_item *items, size_t n, void *d_dst, size_t dst_cap, uint64_t *copied)
+{
+    hipStream_t stream;
+    int st = batch_post_begin(
+        b,
+        [&](size_t streams) {
+            if (!n) return (int)XLZ_OK;
+            if (!items || !d_dst || !xlzpost::pack_items_ok(items, n, streams, dst_cap)) return (int)XLZ_ERR_BAD_ARG;
+            return device_dst_ok(b->ctx, d_dst, dst_cap);
+        },
+        &stream);
+    if (st != XLZ_OK || !n) return st;
+    xlz_pack_stats acc = {};
+    st = batch_pack_run(b, items, n, d_dst, copied, stream, acc);
+    if (st == XLZ_OK) publish_pack(b->ctx, acc);
+    return st;
+}
+
+extern "C" int xlz_ctx_last_pack_stats(xlz_ctx *ctx, xlz_pack_stats *out) { return last_stats(ctx, &xlz_ctx::last_pack, out); }
+
 namespace {
 
 // Moves n chunks from the device to the callers' buffers through the context's pinned ring (one download at a time per
@@ -3074,6 +3185,73 @@ extern "C" int xlz_decode_batch_digests(xlz_ctx *ctx, const xlz_stream_desc *str
 int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post)
 {
     return decode_batch_impl(ctx, streams, n, results, post);
+}
+
+// xlz_check_host.h: the device-destination form, what xlz_xz_decode_device and xlz_7z_decode_device are built on
+int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
+                               const DeviceDest &dest)
+{
+    if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || !dest.dst_off))) return XLZ_ERR_BAD_ARG;
+    if (post_args(post, streams, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    std::vector<xlz_pack_item> items(n);
+    for (size_t i = 0; i < n; i++) items[i].stream = i, items[i].off = 0, items[i].len = dest.want_out[i], items[i].dst_off = dest.dst_off[i];
+    for (size_t k = 0; k < dest.n_copies; k++)
+        if (dest.copies[k].dst_off > dest.cap || dest.copies[k].len > dest.cap - dest.copies[k].dst_off) return XLZ_ERR_BAD_ARG;
+    if (!xlzpost::pack_items_ok(items.data(), n, n, dest.cap)) return XLZ_ERR_BAD_ARG;
+    if (dest.cap) {
+        const int ok = device_dst_ok(ctx, dest.d_dst, dest.cap);
+        if (ok != XLZ_OK) return ok;
+    }
+    xlz_batch *b = nullptr;
+    int st = XLZ_OK;
+    if (n) {
+        st = xlz_batch_create(ctx, streams, n, &b);
+        for (size_t i = 0; i < n && st == XLZ_OK; i++)
+            if (b->plans[i].oversize) st = XLZ_ERR_UNSUPPORTED; // (xlz_decode_batch decodes these as sessions, into host memory)
+        if (st == XLZ_OK) st = xlz_batch_run(b);
+        if (st == XLZ_OK) st = xlz_batch_results(b, results);
+        for (size_t i = 0; i < n && st == XLZ_OK; i++) // the first stream that failed, or that is not what its container says
+            if (results[i].status < 0)
+                st = results[i].status;
+            else if (results[i].out_len != dest.want_out[i] || (dest.want_in && results[i].in_consumed != dest.want_in[i]))
+                st = XLZ_ERR_RESULT;
+        hipStream_t stream = ctx->stream; // (a batch of xlz_batch_create runs there)
+        if (st == XLZ_OK && post.n_steps) {
+            xlz_filter_stats flt = {};
+            st = batch_filter_run(b, post.steps, nullptr, post.n_steps, 0, stream, flt);
+            if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_filter, flt, true);
+        }
+        if (st == XLZ_OK && post.n_ranges) {
+            xlz_check_stats chk = {};
+            xlz_sha256_stats sha = {};
+            std::vector<uint64_t> crc_of(post.digest_out ? post.n_ranges : 0);
+            uint64_t *crc = post.digest_out ? crc_of.data() : post.crc_out;
+            st = batch_checks_run(b, post.ranges, nullptr, post.n_ranges, 0, crc, stream, nullptr, chk);
+            if (st == XLZ_OK && post.digest_out) {
+                st = batch_sha256_run(b, post.ranges, nullptr, post.n_ranges, 0, post.digest_out, stream, nullptr, nullptr, sha);
+                for (size_t q = 0; q < post.n_ranges && st == XLZ_OK; q++)
+                    if (post.ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &post.digest_out[q]);
+            }
+            if (st == XLZ_OK) {
+                xlzpost::stats_add(chk, sha); // (the SHA-256 ranges count in xlz_check_stats too)
+                if (post.digest_out) publish(ctx, &xlz_ctx::last_sha, sha, true, xlzpost::ThresholdIsMax{});
+                publish(ctx, &xlz_ctx::last_check, chk, true);
+            }
+        }
+        if (st == XLZ_OK) {
+            xlz_pack_stats pk = {};
+            st = batch_pack_run(b, items.data(), n, dest.d_dst, nullptr, stream, pk);
+            if (st == XLZ_OK) publish_pack(ctx, pk);
+        }
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) st = st == XLZ_OK ? XLZ_ERR_DEVICE : st;
+    for (size_t k = 0; k < dest.n_copies && st == XLZ_OK; k++)
+        if (dest.copies[k].len && hipMemcpyAsync(static_cast<uint8_t *>(dest.d_dst) + dest.copies[k].dst_off, dest.copies[k].src,
+                                                 (size_t)dest.copies[k].len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            st = XLZ_ERR_DEVICE;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == XLZ_OK) st = XLZ_ERR_DEVICE;
+    xlz_batch_destroy(b);
+    return st;
 }
 
 // Multi-GPU form of xlz_decode_batch.  The streams are independent, and so are the units of an

@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 #include "../../include/xlz.h"
 
@@ -71,6 +73,23 @@ inline void stats_add(xlz_sha256_stats &t, const xlz_sha256_stats &a, ThresholdI
 {
     stats_add(t, a);
     t.threshold = std::max(t.threshold, a.threshold);
+}
+
+// xlz_batch_pack's table as the caller declares it: every item names a stream of the batch, its destination range
+// [dst_off, dst_off + len) lies inside dst_cap (the sum is never formed unless it fits) and no two declared ranges share
+// a byte -- declared, not clipped: what a stream produced must not decide whether a call is well formed.  An item of
+// length 0 declares no byte.
+inline bool pack_items_ok(const xlz_pack_item *items, size_t n, size_t n_streams, uint64_t dst_cap)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> r;
+    for (size_t i = 0; i < n; i++) {
+        if (items[i].stream >= n_streams || items[i].dst_off > dst_cap || items[i].len > dst_cap - items[i].dst_off) return false;
+        if (items[i].len) r.emplace_back(items[i].dst_off, items[i].dst_off + items[i].len);
+    }
+    std::sort(r.begin(), r.end());
+    for (size_t i = 1; i < r.size(); i++)
+        if (r[i - 1].second > r[i].first) return false;
+    return true;
 }
 
 } // namespace xlzpost

@@ -250,8 +250,9 @@ int xz_index(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_b
 // Whole file: index, one batch (block = raw LZMA2 stream, reader2.go:26-41), optional integrity
 // check of every block (CRC32 / CRC64 on host threads; other check types are left unverified
 // and reported through *unverified).
+// d_out: the device-destination form (xlz_xz_decode_device; one context, out == NULL): the decoded file goes to d_out
 static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
-                     uint64_t *out_len, int verify, size_t *unverified);
+                     uint64_t *out_len, int verify, size_t *unverified, void *d_out = nullptr);
 
 extern "C" int xlz_xz_decode(xlz_ctx *ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap, uint64_t *out_len,
                              int verify, size_t *unverified)
@@ -267,12 +268,24 @@ extern "C" int xlz_xz_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uin
     return xz_decode(ctxs, n_ctx, file, len, out, out_cap, out_len, verify, unverified);
 }
 
+// Into device memory: the same parse, the same batch and the same comparisons as xlz_xz_decode; the checks always come
+// from the device (as in check mode 2), and a pack puts the blocks side by side in d_out (xlz_internal_decode_device).
+extern "C" int xlz_xz_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_out, size_t out_cap, uint64_t *out_len,
+                                    int verify, size_t *unverified)
+{
+    if (!ctx || (!d_out && out_cap)) return XLZ_ERR_BAD_ARG;
+    uint8_t none = 0; // (an empty file needs no destination)
+    const int st = xz_decode(&ctx, 1, file, len, nullptr, out_cap, out_len, verify, unverified, d_out ? d_out : &none);
+    if (st != XLZ_OK && out_len) *out_len = 0;
+    return st;
+}
+
 static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
-                     uint64_t *out_len, int verify, size_t *unverified)
+                     uint64_t *out_len, int verify, size_t *unverified, void *d_out)
 {
     for (size_t c = 0; c < n_ctx; c++)
         if (!ctxs[c]) return XLZ_ERR_BAD_ARG;
-    if (!file || (!out && out_cap) || !out_len) return XLZ_ERR_BAD_ARG;
+    if (!file || (!out && out_cap && !d_out) || !out_len) return XLZ_ERR_BAD_ARG;
     *out_len = 0;
     if (unverified) *unverified = 0;
     size_t nb = 0, nfs = 0;
@@ -292,7 +305,7 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         memset(&d[i], 0, sizeof d[i]);
         d[i].in = file + blk[i].comp_off;
         d[i].in_len = (size_t)blk[i].comp_len;
-        d[i].out = out + blk[i].uncomp_off;
+        d[i].out = out ? out + blk[i].uncomp_off : nullptr;
         d[i].out_cap = (size_t)blk[i].uncomp_len;
         d[i].format = XLZ_FMT_LZMA2_RAW;
         d[i].dict_size = blk[i].dict_size;
@@ -301,7 +314,15 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     // batch's results, dg[i] = block i's digest; the other check types stay with the host threads below
     // check mode 2: the SHA-256 blocks join the range list, xdg[i] = block i's 32 bytes (the device's or the host's, as
     // xlz_sha256_plan splits them)
-    const int cmode = verify && n_ctx == 1 ? xlz_ctx_check_mode(ctxs[0]) : 0;
+    // (a device destination: there are no bytes on the host to check, so as mode 2 whatever the context's mode says)
+    const int cmode = !verify ? 0 : d_out ? 2 : n_ctx == 1 ? xlz_ctx_check_mode(ctxs[0]) : 0;
+    std::vector<uint64_t> want_out(d_out ? nb : 0), want_in(d_out ? nb : 0), dst_off(d_out ? nb : 0);
+    for (size_t i = 0; i < nb && d_out; i++) want_out[i] = blk[i].uncomp_len, want_in[i] = blk[i].comp_len, dst_off[i] = blk[i].uncomp_off;
+    DeviceDest dest;
+    dest.d_dst = d_out, dest.cap = out_cap, dest.want_out = want_out.data(), dest.want_in = want_in.data(), dest.dst_off = dst_off.data();
+    auto decode = [&](const PostWork &w) {
+        return d_out ? xlz_internal_decode_device(ctxs[0], d.data(), nb, r.data(), w, dest) : xlz_internal_decode_batch(ctxs[0], d.data(), nb, r.data(), w);
+    };
     const bool dev = cmode == 1 || cmode == 2;
     bool dev_sha = false;
     for (size_t i = 0; i < nb && cmode == 2; i++) dev_sha |= blk[i].check_type == 10;
@@ -328,7 +349,7 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0);
         if (dev_sha) xdg.resize(nb);
         const PostWork w = {fs.data(), nfs, cr.data(), cr.size(), dev_sha ? nullptr : got.data(), dev_sha ? xgot.data() : nullptr, true};
-        st = xlz_internal_decode_batch(ctxs[0], d.data(), nb, r.data(), w);
+        st = decode(w);
         for (size_t k = 0; k < of.size(); k++) {
             if (dev_sha) {
                 xdg[of[k]] = xgot[k];
@@ -338,8 +359,10 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         }
     } else if (chains) { // (the digests, if any, on host threads below: over the filtered bytes)
         xlz_internal_filter_stats_reset(ctxs[0]);
-        st = xlz_internal_decode_batch(ctxs[0], d.data(), nb, r.data(), PostWork{fs.data(), nfs, nullptr, 0, nullptr, nullptr, true});
-    } else
+        st = decode(PostWork{fs.data(), nfs, nullptr, 0, nullptr, nullptr, true});
+    } else if (d_out)
+        st = decode(PostWork{});
+    else
         st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), nb, r.data()) : xlz_decode_batch(ctxs[0], d.data(), nb, r.data());
     if (st != XLZ_OK) return st;
     for (size_t i = 0; i < nb; i++) {
@@ -353,7 +376,7 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         const unsigned nth = (unsigned)std::min<size_t>(std::max<size_t>(1, std::min<unsigned>(hw ? hw : 1, 16)), std::max<size_t>(nb, 1));
         auto work = [&](unsigned t) {
             for (size_t i = t; i < nb; i += nth) {
-                const uint8_t *p = out + blk[i].uncomp_off;
+                const uint8_t *p = out ? out + blk[i].uncomp_off : nullptr; // (a device destination: every check below is the device's)
                 const uint8_t *c = file + blk[i].check_off;
                 if (dev && (blk[i].check_type == 1 || blk[i].check_type == 4))
                     bad[i] = dg[i] != (blk[i].check_type == 1 ? (uint64_t)le32(c) : ((uint64_t)le32(c) | (uint64_t)le32(c + 4) << 32));
