@@ -435,6 +435,61 @@ typedef struct xlz_pack_stats {
 } xlz_pack_stats;
 int xlz_ctx_last_pack_stats(xlz_ctx *ctx, xlz_pack_stats *out);
 
+/* ---- BCJ2 folders of .7z archives (lzma_amd/csrc/xlz_bcj2_dev.hip) ----
+ * Outside the reference.  BCJ2 (method 03 03 01 1B) is what 7-Zip puts in front of LZMA for x86 executables.  It is no
+ * in-place filter: a folder is THREE compressed streams -- main, call, jump -- and a raw range-coder stream, and a serial
+ * merge interleaves them into an output longer than the main stream (the statement of the format is at the head of
+ * lzma_amd/csrc/xlz_bcj2_dev.h).  The merge is a stage of its own between decode and check, with a destination of its own:
+ * one wave per folder, only the decisions serial.                                                       */
+/* The serial merge over host buffers: host only, no device needed.  XLZ_OK: out holds out_len bytes.  XLZ_ERR_RESULT: the
+ * streams do not fill out_len, or a call / jump / rc stream ran out (no stream is read past its end; the contents of out
+ * are unspecified then).  Input left over is ignored.  XLZ_ERR_BAD_ARG: a NULL pointer with a length behind it.   */
+int xlz_bcj2_host(const uint8_t *main_s, size_t main_len, const uint8_t *call_s, size_t call_len, const uint8_t *jump_s,
+                  size_t jump_len, const uint8_t *rc_s, size_t rc_len, uint8_t *out, size_t out_len);
+#define XLZ_BCJ2_RAW (~(uint64_t)0)
+typedef struct xlz_bcj2_src { /* one of main / call / jump: the output of a stream of the batch, or bytes of the caller's */
+    uint64_t stream;    /* index into the batch's streams -- its length is what that stream PRODUCED --, or XLZ_BCJ2_RAW */
+    const uint8_t *raw; /* XLZ_BCJ2_RAW: host memory, uploaded by the call                                       */
+    uint64_t raw_len;
+} xlz_bcj2_src;
+typedef struct xlz_bcj2_item {
+    xlz_bcj2_src main_s, call_s, jump_s;
+    const uint8_t *rc;  /* the range-coder stream: always raw                                                    */
+    uint64_t rc_len;
+    uint64_t out_len;   /* the folder's size                                                                     */
+    uint64_t dst_off;   /* where it goes in the destination                                                      */
+} xlz_bcj2_item;
+typedef struct xlz_bcj2_result {
+    uint64_t produced;  /* out_len for XLZ_OK, else 0 (the item's destination range holds unspecified bytes)     */
+    int32_t status;     /* XLZ_OK; XLZ_ERR_RESULT: the merge failed, or a stream it names did not decode; XLZ_ERR_UNSUPPORTED:
+                           out_len or a stream of 4 GiB or more, or a stream that never sat in the arena          */
+    int32_t reserved;
+} xlz_bcj2_result;
+/* Like xlz_batch_pack it waits for and collects the batch's latest run, then merges every item into ONE caller-owned device
+ * buffer.  One bad item never fails the call.  XLZ_ERR_BAD_ARG, with nothing written: NULL arguments with n > 0; a stream
+ * index >= the batch's streams (other than XLZ_BCJ2_RAW); a raw stream without a pointer; d_dst is not device memory of the
+ * context's device, or dst_cap reaches past its allocation; an item's [dst_off, dst_off + out_len) does not fit in dst_cap;
+ * the declared destination ranges of two items overlap.  Nothing outside the items' ranges is written.  An item longer
+ * than the launch-length cap (0.5 s of one wave: xlzbcj2::kMaxDeviceLen), and every item in bcj2 mode 2, is merged by
+ * xlz_bcj2_host's code on host threads over downloaded streams and uploaded.                              */
+int xlz_batch_bcj2(xlz_batch *batch, const xlz_bcj2_item *items, size_t n, void *d_dst, size_t dst_cap, xlz_bcj2_result *results);
+/* What xlz_7z_decode / xlz_7z_decode_device do with BCJ2 folders.  0 (default): they refuse them (XLZ_ERR_UNSUPPORTED), as
+ * ever.  1: they decode them, merged on the device.  2: as 1, but merged on host threads over downloaded streams and
+ * uploaded -- the fallback path and the A/B yardstick.  The _multi form and the pull readers ignore the mode.  Any other
+ * value: XLZ_ERR_BAD_ARG.                                                                                 */
+int xlz_ctx_set_bcj2_mode(xlz_ctx *ctx, int mode);
+int xlz_ctx_bcj2_mode(const xlz_ctx *ctx);
+/* Of the most recent xlz_batch_bcj2 on `ctx`, or of the most recent xlz_7z_decode / xlz_7z_decode_device in bcj2 mode 1 / 2. */
+typedef struct xlz_bcj2_stats {
+    uint64_t device_items, device_bytes; /* merged by the kernel (bytes of output)                            */
+    uint64_t host_items, host_bytes;     /* merged on host threads: mode 2, or longer than the cap            */
+    uint64_t failed_items;               /* of either: status < 0                                             */
+    double kernel_ms;                    /* the kernel by HIP events                                          */
+    uint32_t launches;
+    uint32_t reserved;
+} xlz_bcj2_stats;
+int xlz_ctx_last_bcj2_stats(xlz_ctx *ctx, xlz_bcj2_stats *out);
+
 /* ---- pull-style readers mirroring the reference's Go surface --------------- */
 /* Constructors take the compressed stream as a buffer (a Go shim slurps its io.Reader
  * first) and copy it.  Constructor-time errors are the ones the reference's
@@ -616,10 +671,12 @@ int xlz_xz_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file,
  * constructors take -- and folders are independent, so an archive is one batch.  Folders with a
  * single LZMA, LZMA2 or Copy coder are decoded; in filter mode 1 (xlz_ctx_set_filter_mode)
  * xlz_7z_decode also takes folders that are a line of Delta / BCJ filters behind one LZMA / LZMA2
- * coder (xlz_7z_index_chains) and undoes the filters on the device between decode and CRC.  Other
- * coder graphs (BCJ2 ...), encryption and external / multi-volume layouts are reported as unsupported.  File names are not parsed: the
+ * coder (xlz_7z_index_chains) and undoes the filters on the device between decode and CRC; in bcj2
+ * mode 1 / 2 (xlz_ctx_set_bcj2_mode) also BCJ2 folders (xlz_7z_index_bcj2), merged on the device.  Other
+ * coder graphs, encryption and external / multi-volume layouts are reported as unsupported.  File names are not parsed: the
  * output is the folders' bytes back to back = the archive's files back to back.                */
-enum { XLZ_7Z_UNSUPPORTED = 0, XLZ_7Z_LZMA = 1, XLZ_7Z_LZMA2 = 2, XLZ_7Z_COPY = 3 };
+enum { XLZ_7Z_UNSUPPORTED = 0, XLZ_7Z_LZMA = 1, XLZ_7Z_LZMA2 = 2, XLZ_7Z_COPY = 3,
+       XLZ_7Z_BCJ2 = 4 /* xlz_7z_index_bcj2 only */ };
 typedef struct xlz_7z_folder {
     uint64_t pack_off;   /* the folder's packed stream inside the file                           */
     uint64_t pack_len;
@@ -655,14 +712,47 @@ int xlz_7z_index(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *f
 int xlz_7z_index_chains(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *folders, size_t max_folders,
                         size_t *n_folders, xlz_7z_substream *substreams, size_t max_substreams, size_t *n_substreams,
                         xlz_filter_step *steps, size_t max_steps, size_t *n_steps, uint64_t *total_unpacked);
+/* xlz_7z_index_chains plus the BCJ2 folders: a folder that is one of the two BCJ2 forms comes back with method
+ * XLZ_7Z_BCJ2 -- here only: xlz_7z_index and xlz_7z_index_chains keep reporting it as method 0 --, unpack_len = the size of
+ * the MERGED bytes (what its CRC and its files' CRCs cover), pack_off / pack_len = its first packed stream, and a record
+ * that places its four streams.  The two forms, found by following the bind pairs and the packed-stream index list:
+ *   four coders: three LZMA / LZMA2 coders (one input, one output each) feeding inputs 0 (main), 1 (call), 2 (jump) of a
+ *   BCJ2 coder (4 inputs, 1 output, no properties); four packed streams: the three coders' inputs and BCJ2's input 3 (rc);
+ *   two coders: one LZMA / LZMA2 coder feeding input 0; call, jump and rc are packed streams read raw.
+ * Everything else stays XLZ_7Z_UNSUPPORTED: other stream counts, properties on BCJ2, an input bound twice, rc fed by a
+ * coder, a sub-coder that is neither LZMA nor LZMA2, filters in front of the sub-coders or behind BCJ2, a call / jump size
+ * that is not a multiple of 4.  bcj2 may be NULL with max_bcj2 0 to obtain the count; XLZ_ERR_OUT_CAP as above.     */
+typedef struct xlz_7z_bcj2_sub {
+    uint64_t pack_off, pack_len; /* inside the file                                                          */
+    uint64_t unpack_len;         /* raw: pack_len                                                             */
+    uint32_t method;             /* XLZ_7Z_LZMA / XLZ_7Z_LZMA2, or XLZ_7Z_COPY: read raw                      */
+    uint32_t dict_size;
+    uint8_t props;
+    uint8_t reserved[7];
+} xlz_7z_bcj2_sub;
+typedef struct xlz_7z_bcj2 {
+    uint64_t folder;             /* index into folders                                                        */
+    xlz_7z_bcj2_sub main_s, call_s, jump_s;
+    uint64_t rc_off, rc_len;
+} xlz_7z_bcj2;
+int xlz_7z_index_bcj2(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *folders, size_t max_folders,
+                      size_t *n_folders, xlz_7z_substream *substreams, size_t max_substreams, size_t *n_substreams,
+                      xlz_filter_step *steps, size_t max_steps, size_t *n_steps, xlz_7z_bcj2 *bcj2, size_t max_bcj2,
+                      size_t *n_bcj2, uint64_t *total_unpacked);
 /* Decode every folder of a .7z archive into out as ONE GPU batch.  verify != 0: CRC32 of every file
  * (or folder) that carries one; *unverified (optional) = folders without any CRC.  XLZ_ERR_UNSUPPORTED
- * when a folder is not a single LZMA / LZMA2 / Copy coder (filter mode 1: nor a chain as above).   */
+ * when a folder is not a single LZMA / LZMA2 / Copy coder (filter mode 1: nor a chain as above; bcj2 mode 1 / 2: nor a
+ * BCJ2 folder).  In bcj2 mode 1 / 2 an archive that HAS a BCJ2 folder is decoded as xlz_7z_decode_device decodes it, into a
+ * device buffer from the context's pool, followed by one download; a BCJ2 folder of 4 GiB or more is XLZ_ERR_UNSUPPORTED, one
+ * whose streams do not decode to their announced sizes or whose merge fails XLZ_ERR_RESULT.  Other archives take the path
+ * they always took.                                                                                     */
 int xlz_7z_decode(xlz_ctx *ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
                   uint64_t *out_len, int verify, size_t *unverified);
 /* xlz_7z_decode into DEVICE memory, as xlz_xz_decode_device: same status, *out_len and *unverified as xlz_7z_decode,
  * except that a folder of 4 GiB or more is XLZ_ERR_UNSUPPORTED.  A Copy folder is uploaded from the file; its CRC is
- * computed on the host over the file's bytes.  About twice the decoded size of device memory.                     */
+ * computed on the host over the file's bytes.  About twice the decoded size of device memory.  In bcj2 mode 1 / 2 the
+ * streams of a BCJ2 folder join the one batch, the folder is merged into d_out behind the pack (xlz_batch_bcj2), and its
+ * CRCs are computed by the check kernels over the destination.                                                     */
 int xlz_7z_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_out, size_t out_cap,
                          uint64_t *out_len, int verify, size_t *unverified);
 /* the same over several contexts (one per GPU; encoded headers are decoded on the first)         */

@@ -163,6 +163,28 @@ class Context:
             raise LzmaError(st, "xlz_ctx_last_pack_stats")
         return {k: getattr(ps, k) for k, _ in N.PackStats._fields_ if k != "reserved"}
 
+    def set_bcj2_mode(self, mode):
+        """what sevenzip_decode / sevenzip_decode_device do with BCJ2 folders (xlz_ctx_set_bcj2_mode): 0 refuse them (default),
+        1 decode them and merge their streams on the device, 2 the same with the merge on host threads"""
+        st = N.lib().xlz_ctx_set_bcj2_mode(self._h, int(mode))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_set_bcj2_mode")
+
+    def bcj2_mode(self):
+        L = N.lib()
+        if not hasattr(L, "xlz_ctx_bcj2_mode"):  # (an older library loaded through XLZ_SO: it refuses every BCJ2 folder)
+            return 0
+        return L.xlz_ctx_bcj2_mode(self._h)
+
+    def last_bcj2_stats(self):
+        """what merged where in the last Batch.bcj2 / sevenzip_decode / sevenzip_decode_device in bcj2 mode 1 / 2 on this
+        context (xlz_ctx_last_bcj2_stats) -> dict"""
+        bs = N.Bcj2Stats()
+        st = N.lib().xlz_ctx_last_bcj2_stats(self._h, ctypes.byref(bs))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_bcj2_stats")
+        return {k: getattr(bs, k) for k, _ in N.Bcj2Stats._fields_ if k != "reserved"}
+
     def event_record(self, slot):
         st = N.lib().xlz_ctx_event_record(self._h, slot)
         if st != OK:
@@ -268,6 +290,26 @@ def filter_host(fid, param, data):
     if st != OK:
         raise LzmaError(st, "xlz_filter_host")
     return buf.raw[: len(data)]
+
+
+def _cbuf(data):
+    """bytes -> (a ctypes buffer that holds them, its address as c_void_p)"""
+    buf = ctypes.create_string_buffer(bytes(data), len(data)) if len(data) else ctypes.create_string_buffer(1)
+    return buf, ctypes.cast(buf, ctypes.c_void_p)
+
+
+def bcj2_host(main, call, jump, rc, out_len):
+    """the BCJ2 merge of a .7z folder's four streams on the host -> bytes (xlz_bcj2_host; no device needed).  Raises
+    LzmaError(ERR_RESULT) when the streams do not fill out_len or one of call / jump / rc runs out"""
+    bufs = [_cbuf(x) for x in (main, call, jump, rc)]
+    out = ctypes.create_string_buffer(max(int(out_len), 1))
+    args = []
+    for (_, p), x in zip(bufs, (main, call, jump, rc)):
+        args += [p, len(x)]
+    st = N.lib().xlz_bcj2_host(*args, ctypes.cast(out, ctypes.c_void_p), int(out_len))
+    if st != OK:
+        raise LzmaError(st, "xlz_bcj2_host")
+    return out.raw[: int(out_len)]
 
 
 def decode_batch_filtered(ctx, streams, steps, checks=()):
@@ -523,6 +565,31 @@ class Batch:
         if st != OK:
             raise LzmaError(st, "xlz_batch_pack")
         return list(copied[:n])
+
+    def bcj2(self, items, dptr, cap):
+        """merge BCJ2 folders into one device buffer, on the device (xlz_batch_bcj2).  items: [(main, call, jump, rc, out_len,
+        dst_off), ...] where main / call / jump are each a stream index of the batch (its decoded output) or bytes (uploaded
+        by the call) and rc is bytes; dptr / cap: device memory of the context's device -> [(status, produced), ...]"""
+        items = list(items)
+        n = len(items)
+        arr = (N.Bcj2Item * max(n, 1))()
+        keep = []
+        for q, (main, call, jump, rc, out_len, dst_off) in enumerate(items):
+            for src, v in ((arr[q].main_s, main), (arr[q].call_s, call), (arr[q].jump_s, jump)):
+                if isinstance(v, int):
+                    src.stream = v
+                else:
+                    buf, p = _cbuf(v)
+                    keep.append(buf)
+                    src.stream, src.raw, src.raw_len = N.BCJ2_RAW, p, len(v)
+            buf, p = _cbuf(rc)
+            keep.append(buf)
+            arr[q].rc, arr[q].rc_len, arr[q].out_len, arr[q].dst_off = p, len(rc), int(out_len), int(dst_off)
+        res = (N.Bcj2Result * max(n, 1))()
+        st = N.lib().xlz_batch_bcj2(self._h, arr, n, ctypes.c_void_p(int(dptr)), int(cap), res)
+        if st != OK:
+            raise LzmaError(st, "xlz_batch_bcj2")
+        return [(res[q].status, res[q].produced) for q in range(n)]
 
     def download(self, i, length):
         buf = ctypes.create_string_buffer(max(int(length), 1))
@@ -906,11 +973,52 @@ def sevenzip_index_chains(data, ctx=None):
             [(steps[i].stream, steps[i].id, steps[i].param) for i in range(nst.value)], total.value)
 
 
+def sevenzip_index_bcj2(data, ctx=None):
+    """sevenzip_index_chains plus the BCJ2 folders (xlz_7z_index_bcj2) -> (folders, files, steps, bcj2, total): a BCJ2 folder
+    has method 4 and the size of its merged bytes, and a record in bcj2: {"folder": index, "main" / "call" / "jump":
+    {pack_off, pack_len, unpack_len, method (1 LZMA, 2 LZMA2, 3 read raw), dict_size, props}, "rc_off", "rc_len"}"""
+    buf, bp = _cbuf(data)
+    h = ctx._h if ctx is not None else None
+    nf, ns, nst, nb, total = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64()
+    st = N.lib().xlz_7z_index_bcj2(h, bp, len(data), None, 0, ctypes.byref(nf), None, 0, ctypes.byref(ns), None, 0, ctypes.byref(nst),
+                                   None, 0, ctypes.byref(nb), ctypes.byref(total))
+    if st != OK:
+        raise LzmaError(st, "xlz_7z_index_bcj2")
+    fo = (N.SzFolder * max(nf.value, 1))()
+    su = (N.SzSubstream * max(ns.value, 1))()
+    steps = (N.FilterStep * max(nst.value, 1))()
+    recs = (N.SzBcj2 * max(nb.value, 1))()
+    st = N.lib().xlz_7z_index_bcj2(h, bp, len(data), fo, nf.value, ctypes.byref(nf), su, ns.value, ctypes.byref(ns), steps, nst.value,
+                                   ctypes.byref(nst), recs, nb.value, ctypes.byref(nb), ctypes.byref(total))
+    if st != OK:
+        raise LzmaError(st, "xlz_7z_index_bcj2")
+    fields = [f for f, _ in N.SzFolder._fields_ if f != "reserved"]
+    sub_fields = [f for f, _ in N.SzBcj2Sub._fields_ if f != "reserved"]
+
+    def sub(s):
+        return {f: getattr(s, f) for f in sub_fields}
+    return ([{f: getattr(fo[i], f) for f in fields} for i in range(nf.value)],
+            [(su[i].size, su[i].crc if su[i].has_crc else None) for i in range(ns.value)],
+            [(steps[i].stream, steps[i].id, steps[i].param) for i in range(nst.value)],
+            [{"folder": recs[i].folder, "main": sub(recs[i].main_s), "call": sub(recs[i].call_s), "jump": sub(recs[i].jump_s),
+              "rc_off": recs[i].rc_off, "rc_len": recs[i].rc_len} for i in range(nb.value)], total.value)
+
+
+def _sevenzip_total(ctx, data):
+    """the decoded size a .7z front-end call on `ctx` will want: with BCJ2 folders in bcj2 mode 1 / 2 (their merged size),
+    with chains in filter mode 1"""
+    if ctx.bcj2_mode() != 0 and hasattr(N.lib(), "xlz_7z_index_bcj2"):
+        return sevenzip_index_bcj2(data, ctx)[4]
+    if ctx.filter_mode() == 1:
+        return sevenzip_index_chains(data, ctx)[3]
+    return sevenzip_index(data, ctx)[2]
+
+
 def sevenzip_decode(ctx, data, verify=True, max_size=None):
     """Decode every folder of a .7z archive as one GPU batch -> the files' bytes back to back.
     max_size: refuse (ERR_OUT_CAP) an archive whose header announces more decoded bytes than that -- the sizes come
     from an untrusted header and the output buffer is allocated from them."""
-    _, _, total = sevenzip_index(data, ctx)
+    total = _sevenzip_total(ctx, data) if ctx.bcj2_mode() != 0 else sevenzip_index(data, ctx)[2]
     if max_size is not None and total > max_size:
         raise LzmaError(ERR_OUT_CAP, "xlz_7z_decode: the archive announces %d bytes, max_size is %d" % (total, max_size))
     buf = ctypes.create_string_buffer(data, len(data))
@@ -971,5 +1079,5 @@ def xz_decode_tensor(ctx, data, verify=True, out=None):
 
 def sevenzip_decode_tensor(ctx, data, verify=True, out=None):
     """sevenzip_decode_device into a torch.uint8 tensor on the context's device, as xz_decode_tensor"""
-    total = sevenzip_index_chains(data, ctx)[3] if ctx.filter_mode() == 1 else sevenzip_index(data, ctx)[2]
+    total = _sevenzip_total(ctx, data)
     return _decode_tensor(sevenzip_decode_device, total, ctx, data, verify, out)

@@ -57,6 +57,7 @@ EXPORTS = [
     "xlz_ctx_last_filter_stats", "xlz_xz_index_chains", "xlz_7z_index_chains",
     "xlz_batch_digests", "xlz_decode_batch_digests", "xlz_sha256_plan", "xlz_ctx_last_sha256_stats",
     "xlz_batch_pack", "xlz_ctx_last_pack_stats", "xlz_xz_decode_device", "xlz_7z_decode_device",
+    "xlz_bcj2_host", "xlz_batch_bcj2", "xlz_ctx_set_bcj2_mode", "xlz_ctx_bcj2_mode", "xlz_ctx_last_bcj2_stats", "xlz_7z_index_bcj2",
 ]
 
 
@@ -130,6 +131,39 @@ class PackStats(ctypes.Structure):
     _fields_ = [("items", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("congruent_items", ctypes.c_uint64),
                 ("empty_items", ctypes.c_uint64), ("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+BCJ2_RAW = 0xFFFFFFFFFFFFFFFF
+SZ_BCJ2 = 4  # xlz_7z_folder.method of a BCJ2 folder (xlz_7z_index_bcj2 only)
+
+
+class Bcj2Src(ctypes.Structure):
+    _fields_ = [("stream", ctypes.c_uint64), ("raw", ctypes.c_void_p), ("raw_len", ctypes.c_uint64)]
+
+
+class Bcj2Item(ctypes.Structure):
+    _fields_ = [("main_s", Bcj2Src), ("call_s", Bcj2Src), ("jump_s", Bcj2Src), ("rc", ctypes.c_void_p), ("rc_len", ctypes.c_uint64),
+                ("out_len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64)]
+
+
+class Bcj2Result(ctypes.Structure):
+    _fields_ = [("produced", ctypes.c_uint64), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Bcj2Stats(ctypes.Structure):
+    _fields_ = [("device_items", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_items", ctypes.c_uint64),
+                ("host_bytes", ctypes.c_uint64), ("failed_items", ctypes.c_uint64), ("kernel_ms", ctypes.c_double),
+                ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SzBcj2Sub(ctypes.Structure):
+    _fields_ = [("pack_off", ctypes.c_uint64), ("pack_len", ctypes.c_uint64), ("unpack_len", ctypes.c_uint64), ("method", ctypes.c_uint32),
+                ("dict_size", ctypes.c_uint32), ("props", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 7)]
+
+
+class SzBcj2(ctypes.Structure):
+    _fields_ = [("folder", ctypes.c_uint64), ("main_s", SzBcj2Sub), ("call_s", SzBcj2Sub), ("jump_s", SzBcj2Sub), ("rc_off", ctypes.c_uint64),
+                ("rc_len", ctypes.c_uint64)]
 
 
 class XzBlock(ctypes.Structure):
@@ -325,6 +359,15 @@ def lib():
         L.xlz_ctx_last_pack_stats.argtypes = [vp, ctypes.POINTER(PackStats)]
         L.xlz_xz_decode_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
         L.xlz_7z_decode_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
+    if hasattr(L, "xlz_bcj2_host"):  # (an older library loaded through XLZ_SO knows no BCJ2 folders)
+        L.xlz_bcj2_host.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, vp, sz]
+        L.xlz_batch_bcj2.argtypes = [vp, ctypes.POINTER(Bcj2Item), sz, vp, sz, ctypes.POINTER(Bcj2Result)]
+        L.xlz_ctx_set_bcj2_mode.argtypes = [vp, i32]
+        L.xlz_ctx_bcj2_mode.argtypes = [vp]
+        L.xlz_ctx_last_bcj2_stats.argtypes = [vp, ctypes.POINTER(Bcj2Stats)]
+        L.xlz_7z_index_bcj2.argtypes = [vp, vp, sz, ctypes.POINTER(SzFolder), sz, ctypes.POINTER(sz), ctypes.POINTER(SzSubstream), sz,
+                                        ctypes.POINTER(sz), ctypes.POINTER(FilterStep), sz, ctypes.POINTER(sz), ctypes.POINTER(SzBcj2), sz,
+                                        ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)]
     _lib = L
     return L
 

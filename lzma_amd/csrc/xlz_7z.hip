@@ -9,8 +9,10 @@
 //
 // Host-only code (no kernels here).  Format restated from 7-Zip's published 7zFormat.txt; nothing
 // of it exists in the reference.  Only what feeds the LZMA paths is implemented: folders with ONE
-// coder that is LZMA, LZMA2 or Copy and one packed stream.  Coder chains (BCJ + LZMA, ...),
-// encryption and multi-volume archives are reported per folder as unsupported.  File names and
+// coder that is LZMA, LZMA2 or Copy and one packed stream; in filter mode 1 lines of Delta / BCJ filters
+// behind one such coder; in bcj2 mode 1 / 2 the two BCJ2 forms (find_bcj2), whose four streams are merged
+// on the device (xlz_bcj2_dev.hip).  Other coder graphs, encryption and multi-volume archives are reported
+// per folder as unsupported.  File names and
 // attributes (FilesInfo) are not parsed: the output is the folders' bytes back to back, which is
 // the archive's files back to back.
 #include <algorithm>
@@ -125,6 +127,18 @@ struct Folder {
     uint32_t chain_method = 0, chain_dict = 0;
     uint8_t chain_props = 0;
     std::vector<std::pair<uint32_t, uint32_t>> steps; // (XLZ_FILTER_*, parameter)
+    // one of the two BCJ2 forms (xlz_7z_index_bcj2, bcj2 mode 1 / 2): for main / call / jump the coder that feeds BCJ2's
+    // input (XLZ_7Z_LZMA / XLZ_7Z_LZMA2 with its properties and the index of its output stream) or XLZ_7Z_COPY for a packed
+    // stream read raw, and which of the folder's packed streams it reads; the packed stream of the range coder; BCJ2's output
+    struct Bcj2Sub {
+        uint32_t method = 0, dict = 0, pack_k = 0, out_index = 0;
+        uint8_t props = 0;
+        uint64_t unpack = 0;
+    };
+    bool bcj2 = false;
+    Bcj2Sub bsub[3];
+    uint32_t rc_pack_k = 0, bcj2_out_index = 0;
+    uint64_t bcj2_final = 0;
 };
 
 // the filter a 7z method id names (7-Zip's Methods.txt), or 0
@@ -151,6 +165,60 @@ struct Streams {
     std::vector<xlz_7z_substream> subs; // in folder order
 };
 
+// Is the coder graph one of the two BCJ2 forms?  nodes: the coders in header order (kind 1 LZMA, 2 LZMA2, 50 BCJ2; input
+// and output streams are numbered through the coders in that order), binds: (input stream, output stream), packed: the
+// input stream every packed stream of the folder feeds.  Four coders: three LZMA / LZMA2 coders feed BCJ2's inputs 0-2;
+// two: one feeds input 0, inputs 1 and 2 are packed streams.  Input 3 (the range coder's bytes) is a packed stream.
+template <class Node>
+void find_bcj2(const std::vector<Node> &nodes, const std::vector<std::pair<uint64_t, uint64_t>> &binds, const std::vector<uint64_t> &packed,
+               Folder &f)
+{
+    const size_t nc = nodes.size();
+    if ((nc != 2 && nc != 4) || packed.size() != 4 || binds.size() != nc - 1) return;
+    std::vector<uint32_t> in_base(nc), out_base(nc);
+    uint32_t ti = 0, to = 0;
+    size_t B = nc;
+    for (size_t c = 0; c < nc; c++) {
+        in_base[c] = ti, out_base[c] = to;
+        ti += nodes[c].n_in, to += nodes[c].n_out;
+        if (nodes[c].kind == 50) {
+            if (B != nc) return;
+            B = c;
+        } else if (nodes[c].kind != XLZ_7Z_LZMA && nodes[c].kind != XLZ_7Z_LZMA2) {
+            return;
+        }
+    }
+    if (B == nc || ti != nc + 3 || to != nc) return;
+    std::vector<int> in_from(ti, -1), in_pack(ti, -1), out_used(to, 0);
+    for (const auto &bp : binds) {
+        if (bp.first >= ti || bp.second >= to || in_from[(size_t)bp.first] >= 0 || out_used[(size_t)bp.second]) return; // (bound twice)
+        in_from[(size_t)bp.first] = (int)bp.second, out_used[(size_t)bp.second] = 1;
+    }
+    for (size_t k = 0; k < 4; k++) {
+        if (packed[k] >= ti || in_from[(size_t)packed[k]] >= 0 || in_pack[(size_t)packed[k]] >= 0) return;
+        in_pack[(size_t)packed[k]] = (int)k;
+    }
+    if (out_used[out_base[B]]) return; // BCJ2's output is the folder's
+    Folder::Bcj2Sub sub[3];
+    for (uint32_t j = 0; j < 3; j++) {
+        const uint32_t in = in_base[B] + j;
+        if (in_from[in] >= 0) {
+            size_t c = 0;
+            while (c < nc && out_base[c] != (uint32_t)in_from[in]) c++;
+            if (c == nc || c == B || in_pack[in_base[c]] < 0) return;
+            sub[j].method = nodes[c].kind, sub[j].props = nodes[c].props, sub[j].dict = nodes[c].dict;
+            sub[j].pack_k = (uint32_t)in_pack[in_base[c]], sub[j].out_index = out_base[c];
+        } else {
+            if (nc == 4 || j == 0) return; // (four coders: all three are fed by coders; two: the main stream is)
+            sub[j].method = XLZ_7Z_COPY, sub[j].pack_k = (uint32_t)in_pack[in];
+        }
+    }
+    if (in_pack[in_base[B] + 3] < 0) return; // (the range coder's bytes fed by a coder)
+    f.bcj2 = true;
+    for (uint32_t j = 0; j < 3; j++) f.bsub[j] = sub[j];
+    f.rc_pack_k = (uint32_t)in_pack[in_base[B] + 3], f.bcj2_out_index = out_base[B];
+}
+
 // one folder (7zFormat.txt "Folder"): coders, bind pairs, packed stream indices
 bool read_folder(Rd &r, Folder &f)
 {
@@ -164,6 +232,11 @@ bool read_folder(Rd &r, Folder &f)
         uint8_t props = 0;
     };
     std::vector<Coder> coders;
+    struct Node { // every coder, for the BCJ2 forms: 1 LZMA, 2 LZMA2, 50 BCJ2 (4 in, 1 out, no properties), 0 anything else
+        uint32_t kind = 0, dict = 0, n_in = 1, n_out = 1;
+        uint8_t props = 0;
+    };
+    std::vector<Node> nodes;
     bool simple = n_coders >= 2 && n_coders <= 4; // every coder one input, one output
     for (uint64_t c = 0; c < n_coders; c++) {
         const uint8_t mb = r.byte();
@@ -188,6 +261,17 @@ bool read_folder(Rd &r, Folder &f)
         }
         total_in += n_in;
         total_out += n_out;
+        {
+            Node nd;
+            nd.n_in = (uint32_t)n_in, nd.n_out = (uint32_t)n_out;
+            if (n_in == 1 && n_out == 1 && id_size == 3 && id[0] == 0x03 && id[1] == 0x01 && id[2] == 0x01 && psz == 5 && !r.bad)
+                nd.kind = XLZ_7Z_LZMA, nd.props = r.p[ppos], nd.dict = le32(r.p + ppos + 1);
+            else if (n_in == 1 && n_out == 1 && id_size == 1 && id[0] == 0x21 && psz == 1 && !r.bad)
+                nd.kind = XLZ_7Z_LZMA2, nd.props = r.p[ppos];
+            else if (n_in == 4 && n_out == 1 && id_size == 4 && id[0] == 0x03 && id[1] == 0x03 && id[2] == 0x01 && id[3] == 0x1B && !(mb & 0x20))
+                nd.kind = 50;
+            nodes.push_back(nd);
+        }
         if (n_in != 1 || n_out != 1) simple = false;
         if (simple) {
             Coder cd;
@@ -219,14 +303,18 @@ bool read_folder(Rd &r, Folder &f)
     const uint64_t n_bind = total_out - 1;
     if (total_in < n_bind) return false;
     std::vector<std::pair<uint64_t, uint64_t>> binds; // (input stream, the output stream that feeds it)
+    std::vector<std::pair<uint64_t, uint64_t>> all_binds;
+    std::vector<uint64_t> packed_list; // the input stream each packed stream feeds
     for (uint64_t k = 0; k < n_bind; k++) {
         const uint64_t in_index = r.number(), out_index = r.number();
         if (simple) binds.emplace_back(in_index, out_index);
+        all_binds.emplace_back(in_index, out_index);
     }
     const uint64_t n_packed = total_in - n_bind;
     if (n_packed == 0) return false; // every folder consumes at least one packed stream
     if (n_packed > 1)
-        for (uint64_t k = 0; k < n_packed; k++) r.number();
+        for (uint64_t k = 0; k < n_packed; k++) packed_list.push_back(r.number());
+    if (!r.bad) find_bcj2(nodes, all_binds, packed_list, f);
     f.method = method;
     f.n_pack = (uint32_t)n_packed;
     f.n_out = (uint32_t)total_out;
@@ -261,7 +349,9 @@ bool read_folder(Rd &r, Folder &f)
     return !r.bad;
 }
 
-int read_streams_info(Rd &r, Streams &s)
+// bcj2: a folder that is one of the BCJ2 forms gets the size of BCJ2's output as its unpack size (bcj2 mode 1 / 2,
+// xlz_7z_index_bcj2); otherwise such a folder is read as ever
+int read_streams_info(Rd &r, Streams &s, bool bcj2 = false)
 {
     uint8_t id = r.byte();
     if (id == kPackInfo) {
@@ -298,6 +388,11 @@ int read_streams_info(Rd &r, Streams &s)
             bool same = true;
             for (uint32_t k = 0; k < f.n_out; k++) {
                 const uint64_t v = r.number();
+                if (f.bcj2) {
+                    for (auto &sb : f.bsub)
+                        if (sb.method != XLZ_7Z_COPY && sb.out_index == k) sb.unpack = v;
+                    if (f.bcj2_out_index == k) f.bcj2_final = v;
+                }
                 if (k + 1 == f.n_out || f.n_out == 1) f.unpack_size = v; // single coder: its one output
                 if (k == 0) main_size = v;
                 same = same && v == main_size;
@@ -305,6 +400,7 @@ int read_streams_info(Rd &r, Streams &s)
             // a chain's filters keep the size: the folder's unpack size is that of the output no bind pair consumes, and
             // every intermediate size must equal it
             if (f.chain && !same) f.chain = false, f.steps.clear();
+            if (f.bcj2 && bcj2) f.unpack_size = f.bcj2_final;
         }
         id = r.byte();
         if (id == kCRC) {
@@ -394,9 +490,11 @@ int read_streams_info(Rd &r, Streams &s)
 // lay the folders of a StreamsInfo out against the file: packed streams follow each other from
 // 32 + PackPos
 // chains: folders that are a chain (Folder::chain) are laid out as their LZMA / LZMA2 coder
-int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> &out, bool chains = false)
+// bcj2: folders that are one of the BCJ2 forms (Folder::bcj2) come back as XLZ_7Z_BCJ2, each with a record in *bcj2
+int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> &out, bool chains = false, std::vector<xlz_7z_bcj2> *bcj2 = nullptr)
 {
     out.clear();
+    if (bcj2) bcj2->clear();
     uint64_t off = 32 + s.pack_pos, uoff = 0;
     size_t pi = 0, si = 0;
     for (const Folder &f0 : s.folders) {
@@ -409,6 +507,30 @@ int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> 
         if (f.n_pack < 1 || pi >= s.pack_sizes.size() || f.n_pack > s.pack_sizes.size() - pi) return XLZ_ERR_RESULT;
         o.pack_off = off;
         o.pack_len = s.pack_sizes[pi];
+        if (bcj2 && f.bcj2 && f.n_pack == 4) {
+            xlz_7z_bcj2 rec;
+            memset(&rec, 0, sizeof rec);
+            rec.folder = out.size();
+            uint64_t offk[4], at = off;
+            for (uint32_t k = 0; k < 4; k++) offk[k] = at, at += s.pack_sizes[pi + k]; // (checked against the file below)
+            bool ok = true;
+            xlz_7z_bcj2_sub *dst[3] = {&rec.main_s, &rec.call_s, &rec.jump_s};
+            for (uint32_t j = 0; j < 3; j++) {
+                const Folder::Bcj2Sub &sb = f.bsub[j];
+                xlz_7z_bcj2_sub &d = *dst[j];
+                d.pack_off = offk[sb.pack_k], d.pack_len = s.pack_sizes[pi + sb.pack_k];
+                d.method = sb.method, d.props = sb.props;
+                d.unpack_len = sb.method == XLZ_7Z_COPY ? d.pack_len : sb.unpack;
+                d.dict_size = sb.method == XLZ_7Z_LZMA2 ? (sb.props == 40 ? 0xFFFFFFFFu : xlz_decode_dict_size2(sb.props)) : sb.dict;
+                if (sb.method == XLZ_7Z_LZMA2 && sb.props > 40) ok = false;
+                if (j && (d.unpack_len & 3)) ok = false; // call / jump: four bytes per operand
+            }
+            rec.rc_off = offk[f.rc_pack_k], rec.rc_len = s.pack_sizes[pi + f.rc_pack_k];
+            if (ok) {
+                o.method = XLZ_7Z_BCJ2;
+                bcj2->push_back(rec);
+            }
+        }
         for (uint32_t k = 0; k < f.n_pack; k++) {
             const uint64_t sz = s.pack_sizes[pi + k];
             if (off > file_len || sz > file_len - off) return XLZ_ERR_UNEXPECTED_EOF;
@@ -438,18 +560,66 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
                    const std::vector<xlz_7z_substream> &subs, uint8_t *out, int verify, size_t *unverified,
                    xlz_ctx *const *ctxs = nullptr, size_t n_ctx = 0, // ctxs: deal the folders to several GPUs (xlz_decode_batch_multi)
                    const std::vector<Folder> *chains = nullptr,      // filter mode 1: the folders' filter steps (Folder::steps)
-                   void *d_out = nullptr, size_t d_cap = 0)          // the device-destination form (xlz_7z_decode_device; out == NULL)
+                   void *d_out = nullptr, size_t d_cap = 0,          // the device-destination form (xlz_7z_decode_device; out == NULL)
+                   const std::vector<xlz_7z_bcj2> *brecs = nullptr, int bcj2_mode = 0) // bcj2 mode 1 / 2 (d_out only): the BCJ2 folders' records
 {
     std::vector<xlz_filter_step> fs;
     std::vector<DeviceCopy> copies; // d_out: the Copy folders go up from the file as they are
     std::vector<uint64_t> want_out, dst_off;
     std::vector<xlz_stream_desc> d;
     std::vector<size_t> which;
+    // BCJ2 folders: their LZMA / LZMA2 sub-streams are further streams of the one batch (no_pack: not packed), the folders
+    // are merged into d_out behind the pack, and their CRCs are taken over the destination (ddg[ddg_first[i] ...] = folder
+    // i's files that carry a CRC, then the folder's own)
+    std::vector<uint8_t> no_pack;
+    std::vector<xlz_bcj2_item> bitems;
+    std::vector<DestRange> dranges;
+    std::vector<size_t> ddg_first(fo.size(), 0);
+    size_t next_rec = 0;
     uint8_t propbuf[5];
     (void)propbuf;
     for (size_t i = 0; i < fo.size(); i++) {
         const xlz_7z_folder &f = fo[i];
         if (f.method == XLZ_7Z_UNSUPPORTED) return XLZ_ERR_UNSUPPORTED;
+        if (f.method == XLZ_7Z_BCJ2) {
+            if (!d_out || !brecs || next_rec >= brecs->size() || (*brecs)[next_rec].folder != i) return XLZ_ERR_UNSUPPORTED;
+            const xlz_7z_bcj2 &rec = (*brecs)[next_rec++];
+            if (f.unpack_len > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED; // (a folder of 4 GiB or more)
+            xlz_bcj2_item it;
+            memset(&it, 0, sizeof it);
+            const xlz_7z_bcj2_sub *sub[3] = {&rec.main_s, &rec.call_s, &rec.jump_s};
+            xlz_bcj2_src *src[3] = {&it.main_s, &it.call_s, &it.jump_s};
+            for (int j = 0; j < 3; j++) {
+                if (sub[j]->method == XLZ_7Z_COPY) { // read raw: it goes up from the file with the call
+                    src[j]->stream = XLZ_BCJ2_RAW, src[j]->raw = file + sub[j]->pack_off, src[j]->raw_len = sub[j]->pack_len;
+                    continue;
+                }
+                xlz_stream_desc s;
+                memset(&s, 0, sizeof s);
+                s.in = file + sub[j]->pack_off, s.in_len = (size_t)sub[j]->pack_len, s.out_cap = (size_t)sub[j]->unpack_len;
+                s.dict_size = sub[j]->dict_size;
+                if (sub[j]->method == XLZ_7Z_LZMA)
+                    s.format = XLZ_FMT_LZMA_RAW, s.props = sub[j]->props, s.unpack_size = sub[j]->unpack_len;
+                else
+                    s.format = XLZ_FMT_LZMA2_RAW;
+                src[j]->stream = d.size();
+                d.push_back(s), which.push_back(i), no_pack.push_back(1);
+                want_out.push_back(sub[j]->unpack_len), dst_off.push_back(0);
+            }
+            it.rc = file + rec.rc_off, it.rc_len = rec.rc_len, it.out_len = f.unpack_len, it.dst_off = f.unpack_off;
+            bitems.push_back(it);
+            if (verify) {
+                ddg_first[i] = dranges.size();
+                uint64_t o = 0;
+                for (uint32_t j = 0; j < f.n_substreams; j++) {
+                    const xlz_7z_substream &ss = subs[f.first_substream + j];
+                    if (ss.has_crc) dranges.push_back(DestRange{f.unpack_off + o, ss.size});
+                    o += ss.size;
+                }
+                if (f.has_crc) dranges.push_back(DestRange{f.unpack_off, f.unpack_len});
+            }
+            continue;
+        }
         if (f.method == XLZ_7Z_COPY) {
             if (f.pack_len != f.unpack_len) return XLZ_ERR_RESULT;
             if (d_out)
@@ -481,11 +651,15 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
                 fs.push_back(q);
             }
         d.push_back(s);
-        which.push_back(i);
+        which.push_back(i), no_pack.push_back(0);
         want_out.push_back(f.unpack_len), dst_off.push_back(f.unpack_off);
     }
     std::vector<xlz_result> r(d.size());
+    std::vector<xlz_bcj2_result> bres(bitems.size());
+    std::vector<uint64_t> ddg(dranges.size());
     DeviceDest dest;
+    dest.no_pack = no_pack.data(), dest.bcj2 = bitems.data(), dest.n_bcj2 = bitems.size(), dest.bcj2_res = bres.data(), dest.bcj2_mode = bcj2_mode;
+    dest.dranges = dranges.data(), dest.n_dranges = dranges.size(), dest.ddigests = ddg.data();
     dest.d_dst = d_out, dest.cap = d_cap, dest.want_out = want_out.data(), dest.dst_off = dst_off.data();
     dest.copies = copies.data(), dest.n_copies = copies.size();
     // (a device destination: one batch with what `w` asks for behind it, the pack and the Copy folders' upload)
@@ -502,6 +676,7 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
     if (dev) {
         std::vector<xlz_check_range> cr;
         for (size_t k = 0; k < which.size(); k++) {
+            if (no_pack[k]) continue; // (a BCJ2 folder's sub-stream: the folder is checked in the destination)
             const xlz_7z_folder &f = fo[which[k]];
             dg_first[which[k]] = cr.size();
             xlz_check_range c;
@@ -536,8 +711,10 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
     }
     for (size_t k = 0; k < d.size(); k++) {
         if (r[k].status < 0) return r[k].status;
-        if (r[k].out_len != fo[which[k]].unpack_len) return XLZ_ERR_RESULT; // a folder decodes to exactly its size
+        if (r[k].out_len != want_out[k]) return XLZ_ERR_RESULT; // a folder (a BCJ2 folder's stream) decodes to exactly its size
     }
+    for (const xlz_bcj2_result &q : bres)
+        if (q.status < 0) return q.status == XLZ_ERR_UNSUPPORTED ? XLZ_ERR_UNSUPPORTED : XLZ_ERR_RESULT; // a merge that failed
     if (verify) {
         size_t nu = 0;
         std::vector<int> bad(fo.size(), 0);
@@ -552,18 +729,20 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
                 uint64_t o = 0;
                 bool any = false;
                 const bool on_dev = dev && f.method != XLZ_7Z_COPY; // (Copy folders never were on the device)
-                size_t q = dg_first[i];
+                const bool on_dst = f.method == XLZ_7Z_BCJ2;        // (merged into the destination and checked there)
+                size_t q = on_dst ? ddg_first[i] : dg_first[i];
+                const std::vector<uint64_t> &dgs = on_dst ? ddg : dg;
                 for (uint32_t k = 0; k < f.n_substreams; k++) {
                     const xlz_7z_substream &ss = subs[f.first_substream + k];
                     if (ss.has_crc) {
                         any = true;
-                        if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(fb + o, (size_t)ss.size)) != ss.crc) bad[i] = 1;
+                        if ((on_dev ? (uint32_t)dgs[q++] : xlzcheck::crc32(fb + o, (size_t)ss.size)) != ss.crc) bad[i] = 1;
                     }
                     o += ss.size;
                 }
                 if (f.has_crc) {
                     any = true;
-                    if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(fb, (size_t)f.unpack_len)) != f.crc) bad[i] = 1;
+                    if ((on_dev ? (uint32_t)dgs[q++] : xlzcheck::crc32(fb, (size_t)f.unpack_len)) != f.crc) bad[i] = 1;
                 }
                 if (!any && !bad[i]) bad[i] = 2;
             }
@@ -606,7 +785,7 @@ int locate_header(const uint8_t *file, size_t len, const uint8_t *&hdr, size_t &
 
 // the archive's MAIN StreamsInfo.  An encoded header (what 7-Zip writes by default) is itself a
 // folder: it is decoded with the batch engine first (needs ctx).
-int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std::vector<uint8_t> &decoded_header)
+int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std::vector<uint8_t> &decoded_header, bool bcj2 = false)
 {
     const uint8_t *hdr;
     size_t hl;
@@ -646,7 +825,7 @@ int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std:
             t = r.byte();
         }
         if (t == kAdditionalStreamsInfo) return XLZ_ERR_UNSUPPORTED;
-        if (t == kMainStreamsInfo) return read_streams_info(r, s);
+        if (t == kMainStreamsInfo) return read_streams_info(r, s, bcj2);
         return r.bad ? XLZ_ERR_RESULT : XLZ_OK; // no streams: only empty files
     }
     return XLZ_ERR_UNSUPPORTED;
@@ -724,6 +903,51 @@ extern "C" int xlz_7z_index_chains(xlz_ctx *ctx, const uint8_t *file, size_t len
     return XLZ_OK;
 }
 
+// xlz_7z_index_chains plus the BCJ2 folders: method XLZ_7Z_BCJ2, the size of the merged bytes, and a record each that
+// places main, call, jump and the range coder's bytes inside the file.
+extern "C" int xlz_7z_index_bcj2(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_folder *folders, size_t max_folders, size_t *n_folders,
+                                 xlz_7z_substream *substreams, size_t max_substreams, size_t *n_substreams, xlz_filter_step *steps,
+                                 size_t max_steps, size_t *n_steps, xlz_7z_bcj2 *bcj2, size_t max_bcj2, size_t *n_bcj2, uint64_t *total_unpacked)
+{
+    if (!file || !n_folders || !n_steps || !n_bcj2 || (!folders && max_folders) || (!substreams && max_substreams) || (!steps && max_steps) ||
+        (!bcj2 && max_bcj2))
+        return XLZ_ERR_BAD_ARG;
+    *n_folders = 0, *n_steps = 0, *n_bcj2 = 0;
+    if (n_substreams) *n_substreams = 0;
+    if (total_unpacked) *total_unpacked = 0;
+    Streams s;
+    std::vector<uint8_t> dh;
+    int st = main_streams(ctx, file, len, s, dh, true);
+    if (st != XLZ_OK) return st;
+    std::vector<xlz_7z_folder> fo;
+    std::vector<xlz_7z_bcj2> recs;
+    st = place_folders(s, len, fo, true, &recs);
+    if (st != XLZ_OK) return st;
+    uint64_t total = 0;
+    size_t ns = 0;
+    for (size_t i = 0; i < fo.size(); i++) {
+        if (i < max_folders) folders[i] = fo[i];
+        total += fo[i].unpack_len;
+        if (s.folders[i].chain)
+            for (const auto &stp : s.folders[i].steps) {
+                if (ns < max_steps) {
+                    memset(&steps[ns], 0, sizeof steps[ns]);
+                    steps[ns].stream = i, steps[ns].id = stp.first, steps[ns].param = stp.second;
+                }
+                ns++;
+            }
+    }
+    for (size_t i = 0; i < s.subs.size() && i < max_substreams; i++) substreams[i] = s.subs[i];
+    for (size_t i = 0; i < recs.size() && i < max_bcj2; i++) bcj2[i] = recs[i];
+    *n_folders = fo.size(), *n_steps = ns, *n_bcj2 = recs.size();
+    if (n_substreams) *n_substreams = s.subs.size();
+    if (total_unpacked) *total_unpacked = total;
+    if ((max_folders && fo.size() > max_folders) || (max_substreams && s.subs.size() > max_substreams) || (max_steps && ns > max_steps) ||
+        (max_bcj2 && recs.size() > max_bcj2))
+        return XLZ_ERR_OUT_CAP;
+    return XLZ_OK;
+}
+
 static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out, size_t out_cap,
                      uint64_t *out_len, int verify, size_t *unverified, void *d_out = nullptr);
 
@@ -765,19 +989,42 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     *out_len = 0;
     if (unverified) *unverified = 0;
     if (verify && n_ctx == 1 && (d_out || xlz_ctx_check_mode(ctx) >= 1)) xlz_internal_check_stats_reset(ctx); // (an encoded header's batch counts too)
+    // bcj2 mode 1 / 2 (xlz_ctx_set_bcj2_mode; one context): BCJ2 folders are decoded, merged into device memory
+    const int bmode = n_ctx == 1 ? xlz_ctx_bcj2_mode(ctx) : 0;
+    if (bmode > 0) xlz_internal_bcj2_stats_reset(ctx);
     Streams s;
     std::vector<uint8_t> dh;
-    int st = main_streams(ctx, file, len, s, dh);
+    int st = main_streams(ctx, file, len, s, dh, bmode > 0);
     if (st != XLZ_OK) return st;
     // filter mode 1 (xlz_ctx_set_filter_mode; one context): folders that are a chain of filters behind an LZMA / LZMA2 coder
     const bool chains = n_ctx == 1 && xlz_ctx_filter_mode(ctx) == 1;
     if (chains) xlz_internal_filter_stats_reset(ctx);
     std::vector<xlz_7z_folder> fo;
-    st = place_folders(s, len, fo, chains);
+    std::vector<xlz_7z_bcj2> brecs;
+    st = place_folders(s, len, fo, chains, bmode > 0 ? &brecs : nullptr);
     if (st != XLZ_OK) return st;
     uint64_t total = 0;
     for (auto &f : fo) total += f.unpack_len;
     if (total > out_cap) return XLZ_ERR_OUT_CAP;
+    if (!brecs.empty()) {
+        // an archive that HAS a BCJ2 folder: the device-destination path -- for a host destination into a block from the
+        // context's pool, followed by one download
+        for (auto &f : fo)
+            if (f.method == XLZ_7Z_UNSUPPORTED) return XLZ_ERR_UNSUPPORTED;
+        void *blk = nullptr;
+        if (!d_out) {
+            st = xlz_internal_device_block(ctx, (size_t)total, &blk);
+            if (st != XLZ_OK) return st;
+            if (verify) xlz_internal_check_stats_reset(ctx);
+        }
+        st = decode_folders(ctx, file, fo, s.subs, nullptr, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr, d_out ? d_out : blk,
+                            d_out ? out_cap : (size_t)total, &brecs, bmode);
+        if (st == XLZ_OK && blk) st = xlz_internal_device_block_download(ctx, blk, out, (size_t)total);
+        xlz_internal_device_block_release(ctx, blk);
+        if (st != XLZ_OK) return st;
+        *out_len = total;
+        return XLZ_OK;
+    }
     st = decode_folders(ctx, file, fo, s.subs, out, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr, d_out, out_cap);
     if (st != XLZ_OK) return st;
     *out_len = total;

@@ -22,13 +22,34 @@ struct DeviceCopy {
     const uint8_t *src;
     uint64_t len;
 };
+struct DestRange { // bytes of the destination, for a CRC32 over them
+    uint64_t off, len;
+};
 struct DeviceDest {
     void *d_dst = nullptr;
     size_t cap = 0;
     const uint64_t *want_out = nullptr, *want_in = nullptr, *dst_off = nullptr;
     const DeviceCopy *copies = nullptr;
     size_t n_copies = 0;
+    // .7z BCJ2 folders (bcj2 mode 1 / 2): no_pack[i] != 0 -- stream i is a sub-stream of one, it must still produce
+    // want_out[i] bytes but is not packed; the folders are merged into d_dst behind the pack (items as xlz_batch_bcj2 takes
+    // them, bcj2_res[] their outcomes, bcj2_mode 1: on the device, 2: on host threads), and the CRC32 of dranges[] of the
+    // DESTINATION -- the merged bytes never sit in the arena -- goes to ddigests[]
+    const uint8_t *no_pack = nullptr;
+    const xlz_bcj2_item *bcj2 = nullptr;
+    size_t n_bcj2 = 0;
+    xlz_bcj2_result *bcj2_res = nullptr;
+    int bcj2_mode = 1;
+    const DestRange *dranges = nullptr;
+    size_t n_dranges = 0;
+    uint64_t *ddigests = nullptr;
 };
+// a device block of at least `bytes` from the context's pool (xlz_7z_decode with a BCJ2 folder decodes into one), its
+// download into host memory once the context's stream has drained, and its return
+int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p);
+int xlz_internal_device_block_download(xlz_ctx *ctx, const void *p, uint8_t *dst, size_t bytes);
+void xlz_internal_device_block_release(xlz_ctx *ctx, void *p);
+void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx);
 // The device-destination form of xlz_internal_decode_batch (streams[i].out is NULL): one batch -- create, run, results,
 // the size checks above (a stream's own failure, then XLZ_ERR_RESULT), post.steps, post.ranges (exactly one of crc_out /
 // digest_out when there are ranges; the statistics always accumulate), the pack into dest, the copies, and a wait for

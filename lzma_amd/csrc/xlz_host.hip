@@ -33,6 +33,7 @@
 #include "xlz_sha256_dev.h"
 #include "xlz_filter_dev.h"
 #include "xlz_pack_dev.h"
+#include "xlz_bcj2_dev.h"
 
 using namespace xlz;
 
@@ -251,6 +252,9 @@ struct xlz_ctx {
     int filter_mode = 0;
     xlz_filter_stats last_filter = {};
     xlz_pack_stats last_pack = {}; // xlz_ctx_last_pack_stats (xlz_pack_dev.hip)
+    // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
+    int bcj2_mode = 0;
+    xlz_bcj2_stats last_bcj2 = {};
 };
 
 // Scratch of one kind of post-decode kernel of a batch: device and pinned memory from where the batch's memory comes
@@ -342,7 +346,8 @@ struct xlz_batch {
     // the post-decode stage's scratch (PostScratch), one per kind of kernel.  Checks: range table | segment values |
     // digests on the device, range table | digests pinned.  SHA-256: digests | range table on both sides.  Filters: step
     // tables | window table | rows of sums on the device, the step tables pinned.  Pack: the item table on both sides.
-    PostScratch chk, sha, flt, pk;
+    // BCJ2: item table | raw streams | results on both sides.
+    PostScratch chk, sha, flt, pk, bj;
 };
 
 // ---------------------------------------------------------------- helpers ----
@@ -853,6 +858,7 @@ int batch_free(xlz_batch *b)
     b->sha.release(b);
     b->flt.release(b);
     b->pk.release(b);
+    b->bj.release(b);
     delete b;
     return XLZ_OK;
 }
@@ -2389,6 +2395,309 @@ extern "C" int xlz_batch_pack(xlz_batch *b, const xlz_pack_item *items, size_t n
 
 extern "C" int xlz_ctx_last_pack_stats(xlz_ctx *ctx, xlz_pack_stats *out) { return last_stats(ctx, &xlz_ctx::last_pack, out); }
 
+// ---------------------------------------------------------------- BCJ2 folders ----
+namespace xlz {
+int bcj2_launch(const xlzbcj2::DevItem *items, uint32_t n_items, uint8_t *dst, xlzbcj2::DevResult *results, int num_cus, hipStream_t stream);
+}
+
+namespace {
+
+// a stream's line loads reach the next multiple of 16 behind its length (xlz_bcj2_dev.h): inside its region of the arena
+static_assert(kOutTailPad >= 16 && kArenaAlign % 16 == 0, "xlz_bcj2_dev.h reads whole lines of a stream in the arena");
+
+// xlz_batch_bcj2's table as the caller declares it (cf. xlzpost::pack_items_ok)
+bool bcj2_items_ok(const xlz_bcj2_item *items, size_t n, size_t n_streams, uint64_t dst_cap)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> r;
+    for (size_t i = 0; i < n; i++) {
+        const xlz_bcj2_item &it = items[i];
+        for (const xlz_bcj2_src *s : {&it.main_s, &it.call_s, &it.jump_s})
+            if (s->stream == XLZ_BCJ2_RAW ? (!s->raw && s->raw_len) : s->stream >= n_streams) return false;
+        if ((!it.rc && it.rc_len) || it.dst_off > dst_cap || it.out_len > dst_cap - it.dst_off) return false;
+        if (it.out_len) r.emplace_back(it.dst_off, it.dst_off + it.out_len);
+    }
+    std::sort(r.begin(), r.end());
+    for (size_t i = 1; i < r.size(); i++)
+        if (r[i - 1].second > r[i].first) return false;
+    return true;
+}
+
+// one of an item's four streams, resolved against a collected batch
+struct Bcj2Src {
+    const uint8_t *host = nullptr; // raw: the caller's bytes
+    const uint8_t *dev = nullptr;  // a stream of the batch: where its output lies in the arena
+    uint64_t len = 0;
+};
+int bcj2_resolve(xlz_batch *b, const xlz_bcj2_src &s, Bcj2Src &o)
+{
+    if (s.stream == XLZ_BCJ2_RAW) {
+        o.host = s.raw, o.len = s.raw_len;
+    } else {
+        const size_t k = (size_t)s.stream;
+        if (b->final_results[k].status < 0) return XLZ_ERR_RESULT; // a stream that did not decode merges into nothing
+        const xlzpost::Clip c = xlzpost::clip(stream_out(b, k, nullptr), 0, xlzpost::kWholeStream);
+        if (c.place != xlzpost::Place::Arena && c.place != xlzpost::Place::Empty) return XLZ_ERR_UNSUPPORTED;
+        o.dev = b->d_out + b->plans[k].out_off, o.len = c.hi;
+    }
+    return o.len > 0xFFFFFFFFull ? XLZ_ERR_UNSUPPORTED : XLZ_OK;
+}
+
+// Merges items[0 .. n) (accepted by bcj2_items_ok) of a COLLECTED batch into d_dst and waits: by the merge kernel on
+// `stream` (mode 1, items up to xlzbcj2::kMaxDeviceLen), the others by xlzbcj2::host_merge on host threads over downloaded
+// streams, uploaded afterwards.  results[] is indexed like items[].
+int batch_bcj2_run(xlz_batch *b, const xlz_bcj2_item *items, size_t n, void *d_dst, xlz_bcj2_result *results, hipStream_t stream, int mode,
+                   xlz_bcj2_stats &acc)
+{
+    using namespace xlzbcj2;
+    if (!n) return XLZ_OK;
+    struct Item {
+        Bcj2Src s[3];
+    };
+    std::vector<Item> res(n);
+    std::vector<size_t> on_dev, on_host;
+    for (size_t i = 0; i < n; i++) {
+        const xlz_bcj2_item &it = items[i];
+        int st = it.out_len > 0xFFFFFFFFull || it.rc_len > 0xFFFFFFFFull ? (int)XLZ_ERR_UNSUPPORTED : (int)XLZ_OK;
+        const xlz_bcj2_src *src[3] = {&it.main_s, &it.call_s, &it.jump_s};
+        for (int k = 0; k < 3 && st == XLZ_OK; k++) st = bcj2_resolve(b, *src[k], res[i].s[k]);
+        results[i].produced = 0, results[i].status = st, results[i].reserved = 0;
+        if (st != XLZ_OK)
+            acc.failed_items++;
+        else
+            (mode == 1 && it.out_len <= kMaxDeviceLen ? on_dev : on_host).push_back(i);
+    }
+    xlz_ctx *ctx = b->ctx;
+    if (!on_dev.empty()) {
+        if (on_dev.size() > 0xFFFFFFFFull || ((uintptr_t)b->d_out & 15)) return XLZ_ERR_UNSUPPORTED;
+        // item table | raw streams, each at a multiple of kStreamAlign | results
+        const size_t tab_bytes = (size_t)padded(on_dev.size() * sizeof(DevItem));
+        uint64_t raw_bytes = 0;
+        for (size_t i : on_dev) {
+            for (int k = 0; k < 3; k++)
+                if (res[i].s[k].host) raw_bytes += padded(res[i].s[k].len);
+            raw_bytes += padded(items[i].rc_len);
+        }
+        const size_t res_off = tab_bytes + (size_t)raw_bytes, res_bytes = on_dev.size() * sizeof(DevResult);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        int st = b->bj.reserve(b, res_off + res_bytes, res_off + res_bytes);
+        if (st != XLZ_OK) return st;
+        if ((uintptr_t)b->bj.dev & 15) return XLZ_ERR_UNSUPPORTED;
+        DevItem *h_tab = reinterpret_cast<DevItem *>(b->bj.pin);
+        size_t at = tab_bytes;
+        auto stage = [&](const uint8_t *p, uint64_t len) { // -> where the bytes will lie on the device
+            if (len) memcpy(b->bj.pin + at, p, (size_t)len);
+            const uint8_t *d = b->bj.dev + at;
+            at += (size_t)padded(len);
+            return d;
+        };
+        for (size_t q = 0; q < on_dev.size(); q++) {
+            const size_t i = on_dev[q];
+            DevItem d;
+            memset(&d, 0, sizeof d);
+            const uint8_t *ptr[3];
+            for (int k = 0; k < 3; k++) ptr[k] = res[i].s[k].host ? stage(res[i].s[k].host, res[i].s[k].len) : res[i].s[k].dev;
+            d.main = ptr[0], d.call = ptr[1], d.jump = ptr[2], d.rc = stage(items[i].rc, items[i].rc_len);
+            d.main_len = (uint32_t)res[i].s[0].len, d.call_len = (uint32_t)res[i].s[1].len, d.jump_len = (uint32_t)res[i].s[2].len;
+            d.rc_len = (uint32_t)items[i].rc_len, d.dst = items[i].dst_off, d.out_len = (uint32_t)items[i].out_len;
+            h_tab[q] = d;
+        }
+        HIP_TRY(hipMemcpyAsync(b->bj.dev, b->bj.pin, res_off, hipMemcpyHostToDevice, stream));
+        float ms = 0;
+        st = timed_bracket(
+            stream, b->bj, "bcj2 kernel", &ms,
+            [&] {
+                return xlz::bcj2_launch(reinterpret_cast<const DevItem *>(b->bj.dev), (uint32_t)on_dev.size(), static_cast<uint8_t *>(d_dst),
+                                        reinterpret_cast<DevResult *>(b->bj.dev + res_off), ctx->num_cus, stream) == 0;
+            },
+            b->bj.pin + res_off, b->bj.dev + res_off, res_bytes);
+        if (st != XLZ_OK) return st;
+        const DevResult *h_res = reinterpret_cast<const DevResult *>(b->bj.pin + res_off);
+        for (size_t q = 0; q < on_dev.size(); q++) {
+            const size_t i = on_dev[q];
+            const bool ok = h_res[q].status == kStOk && h_res[q].produced == items[i].out_len;
+            results[i].status = ok ? XLZ_OK : XLZ_ERR_RESULT, results[i].produced = ok ? items[i].out_len : 0;
+            acc.device_items++, acc.device_bytes += items[i].out_len, acc.failed_items += !ok;
+        }
+        acc.kernel_ms += ms, acc.launches++;
+    }
+    if (!on_host.empty()) {
+        // the streams of the batch come down, the merged folders go up; the merges run side by side in between
+        std::vector<std::vector<uint8_t>> down(3 * on_host.size()), merged(on_host.size());
+        {
+            std::lock_guard<std::mutex> lock(ctx->mu);
+            HIP_TRY(hipSetDevice(ctx->device));
+            HIP_TRY(hipStreamSynchronize(stream));
+            for (size_t q = 0; q < on_host.size(); q++)
+                for (int k = 0; k < 3; k++) {
+                    const Bcj2Src &s = res[on_host[q]].s[k];
+                    if (!s.dev || !s.len) continue;
+                    down[3 * q + k].resize((size_t)s.len);
+                    HIP_TRY(hipMemcpy(down[3 * q + k].data(), s.dev, (size_t)s.len, hipMemcpyDeviceToHost));
+                }
+        }
+        std::vector<int> status(on_host.size(), XLZ_OK);
+        std::atomic<size_t> next{0};
+        auto work = [&] {
+            for (size_t q; (q = next.fetch_add(1)) < on_host.size();) {
+                const size_t i = on_host[q];
+                const uint8_t *p[3];
+                for (int k = 0; k < 3; k++) p[k] = res[i].s[k].host ? res[i].s[k].host : down[3 * q + k].data();
+                merged[q].resize((size_t)items[i].out_len);
+                status[q] = host_merge(p[0], (size_t)res[i].s[0].len, p[1], (size_t)res[i].s[1].len, p[2], (size_t)res[i].s[2].len, items[i].rc,
+                                       (size_t)items[i].rc_len, merged[q].data(), merged[q].size(), nullptr) == kStOk
+                                ? XLZ_OK
+                                : XLZ_ERR_RESULT;
+            }
+        };
+        const unsigned hw = std::thread::hardware_concurrency();
+        const unsigned nth = (unsigned)std::min<size_t>(std::max(1u, std::min(hw ? hw : 1u, 16u)), on_host.size());
+        std::vector<std::thread> th;
+        try {
+            for (unsigned t = 1; t < nth; t++) th.emplace_back(work);
+        } catch (...) { // (no thread to be had: this one does it all)
+        }
+        work();
+        for (auto &x : th) x.join();
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        for (size_t q = 0; q < on_host.size(); q++) {
+            const size_t i = on_host[q];
+            const bool ok = status[q] == XLZ_OK;
+            if (ok && items[i].out_len)
+                HIP_TRY(hipMemcpy(static_cast<uint8_t *>(d_dst) + items[i].dst_off, merged[q].data(), merged[q].size(), hipMemcpyHostToDevice));
+            results[i].status = status[q], results[i].produced = ok ? items[i].out_len : 0;
+            acc.host_items++, acc.host_bytes += items[i].out_len, acc.failed_items += !ok;
+        }
+    }
+    return XLZ_OK;
+}
+
+void publish_bcj2(xlz_ctx *ctx, const xlz_bcj2_stats &v, bool accumulate)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (!accumulate) ctx->last_bcj2 = xlz_bcj2_stats{};
+    xlz_bcj2_stats &t = ctx->last_bcj2;
+    t.device_items += v.device_items, t.device_bytes += v.device_bytes, t.host_items += v.host_items, t.host_bytes += v.host_bytes;
+    t.failed_items += v.failed_items, t.kernel_ms += v.kernel_ms, t.launches += v.launches;
+}
+
+// The CRC32 of ranges of a caller-owned DEVICE buffer (the merged BCJ2 folders of xlz_7z_decode_device), by the check
+// kernels on `stream` with the batch's check scratch; waits.  The kernels read aligned lines: their base is d_dst rounded
+// down to 16, and nothing outside a range is read.
+int dest_checks_run(xlz_batch *b, const void *d_dst, const DestRange *ranges, size_t n, uint64_t *digests, hipStream_t stream, xlz_check_stats &acc)
+{
+    using xlzchk::DevRange;
+    const uint64_t mis = (uintptr_t)d_dst & 15;
+    std::vector<DevRange> dev;
+    std::vector<size_t> where;
+    uint64_t segs = 0, dev_bytes = 0;
+    for (size_t q = 0; q < n; q++) {
+        digests[q] = 0;
+        if (!ranges[q].len) {
+            acc.empty_ranges++;
+            continue;
+        }
+        DevRange d;
+        d.off = ranges[q].off + mis, d.len = ranges[q].len;
+        const uint64_t ns = xlzchk::range_segments(d.off, d.len);
+        if (segs + ns > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+        d.seg_first = (uint32_t)segs, d.n_segs = (uint32_t)ns, d.out_index = (uint32_t)dev.size(), d.reserved = 0;
+        segs += ns, dev_bytes += d.len;
+        dev.push_back(d), where.push_back(q);
+    }
+    if (dev.empty()) return XLZ_OK;
+    xlz_ctx *ctx = b->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    int st = check_tables(ctx);
+    if (st != XLZ_OK) return st;
+    const size_t tab_bytes = dev.size() * sizeof(DevRange), seg_bytes = (size_t)segs * 8, dig_bytes = dev.size() * 8;
+    st = b->chk.reserve(b, tab_bytes + seg_bytes + dig_bytes, tab_bytes + dig_bytes);
+    if (st != XLZ_OK) return st;
+    memcpy(b->chk.pin, dev.data(), tab_bytes);
+    uint64_t *h_dig = reinterpret_cast<uint64_t *>(b->chk.pin + tab_bytes);
+    DevRange *d_tab = reinterpret_cast<DevRange *>(b->chk.dev);
+    uint64_t *d_seg = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes), *d_dig = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes + seg_bytes);
+    HIP_TRY(hipMemcpyAsync(d_tab, b->chk.pin, tab_bytes, hipMemcpyHostToDevice, stream));
+    float ms = 0;
+    st = timed_bracket(
+        stream, b->chk, "check kernels", &ms,
+        [&] {
+            return xlz::check_launch(32, static_cast<const uint8_t *>(d_dst) - mis, d_tab, (uint32_t)dev.size(), (uint32_t)segs, ctx->chk_tab[0],
+                                     ctx->chk_consts[0], d_seg, d_dig, ctx->num_cus, stream) == 0;
+        },
+        h_dig, d_dig, dig_bytes);
+    if (st != XLZ_OK) return st;
+    for (size_t j = 0; j < dev.size(); j++) digests[where[j]] = h_dig[j];
+    acc.device_ranges += dev.size(), acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches++;
+    return XLZ_OK;
+}
+
+} // namespace
+
+extern "C" int xlz_bcj2_host(const uint8_t *main_s, size_t main_len, const uint8_t *call_s, size_t call_len, const uint8_t *jump_s,
+                             size_t jump_len, const uint8_t *rc_s, size_t rc_len, uint8_t *out, size_t out_len)
+{
+    if ((!main_s && main_len) || (!call_s && call_len) || (!jump_s && jump_len) || (!rc_s && rc_len) || (!out && out_len)) return XLZ_ERR_BAD_ARG;
+    return xlzbcj2::host_merge(main_s, main_len, call_s, call_len, jump_s, jump_len, rc_s, rc_len, out, out_len, nullptr) == xlzbcj2::kStOk
+               ? XLZ_OK
+               : XLZ_ERR_RESULT;
+}
+
+extern "C" int xlz_batch_bcj2(xlz_batch *b, const xlz_bcj2_item *items, size_t n, void *d_dst, size_t dst_cap, xlz_bcj2_result *results)
+{
+    hipStream_t stream;
+    int st = batch_post_begin(
+        b,
+        [&](size_t streams) {
+            if (!n) return (int)XLZ_OK;
+            if (!items || !results || !d_dst || !bcj2_items_ok(items, n, streams, dst_cap)) return (int)XLZ_ERR_BAD_ARG;
+            return device_dst_ok(b->ctx, d_dst, dst_cap);
+        },
+        &stream);
+    if (st != XLZ_OK || !n) return st;
+    xlz_bcj2_stats acc = {};
+    st = batch_bcj2_run(b, items, n, d_dst, results, stream, xlz_ctx_bcj2_mode(b->ctx) == 2 ? 2 : 1, acc);
+    if (st == XLZ_OK) publish_bcj2(b->ctx, acc, false);
+    return st;
+}
+
+extern "C" int xlz_ctx_set_bcj2_mode(xlz_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 2) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->bcj2_mode = mode;
+    return XLZ_OK;
+}
+extern "C" int xlz_ctx_bcj2_mode(const xlz_ctx *ctx) { return ctx ? ctx->bcj2_mode : XLZ_ERR_BAD_ARG; }
+extern "C" int xlz_ctx_last_bcj2_stats(xlz_ctx *ctx, xlz_bcj2_stats *out) { return last_stats(ctx, &xlz_ctx::last_bcj2, out); }
+
+void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx) { publish_bcj2(ctx, xlz_bcj2_stats{}, false); }
+
+int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p)
+{
+    if (!ctx || !p) return XLZ_ERR_BAD_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    *p = ctx->pool.take(bytes, false);
+    return *p ? XLZ_OK : XLZ_ERR_DEVICE;
+}
+int xlz_internal_device_block_download(xlz_ctx *ctx, const void *p, uint8_t *dst, size_t bytes)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (bytes) HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+    return XLZ_OK;
+}
+void xlz_internal_device_block_release(xlz_ctx *ctx, void *p)
+{
+    if (!p) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream); // (a block must not return to the pool while work still uses it)
+    ctx->pool.give(p);
+    ctx->pool.end_of_call();
+}
+
 namespace {
 
 // Moves n chunks from the device to the callers' buffers through the context's pinned ring (one download at a time per
@@ -3193,11 +3502,15 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
 {
     if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || !dest.dst_off))) return XLZ_ERR_BAD_ARG;
     if (post_args(post, streams, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
-    std::vector<xlz_pack_item> items(n);
-    for (size_t i = 0; i < n; i++) items[i].stream = i, items[i].off = 0, items[i].len = dest.want_out[i], items[i].dst_off = dest.dst_off[i];
+    std::vector<xlz_pack_item> items;
+    for (size_t i = 0; i < n; i++)
+        if (!(dest.no_pack && dest.no_pack[i])) items.push_back(xlz_pack_item{i, 0, dest.want_out[i], dest.dst_off[i]});
     for (size_t k = 0; k < dest.n_copies; k++)
         if (dest.copies[k].dst_off > dest.cap || dest.copies[k].len > dest.cap - dest.copies[k].dst_off) return XLZ_ERR_BAD_ARG;
-    if (!xlzpost::pack_items_ok(items.data(), n, n, dest.cap)) return XLZ_ERR_BAD_ARG;
+    if (!xlzpost::pack_items_ok(items.data(), items.size(), n, dest.cap)) return XLZ_ERR_BAD_ARG;
+    if (dest.n_bcj2 && (!n || !dest.bcj2 || !dest.bcj2_res || !bcj2_items_ok(dest.bcj2, dest.n_bcj2, n, dest.cap))) return XLZ_ERR_BAD_ARG;
+    for (size_t q = 0; q < dest.n_dranges; q++)
+        if (!dest.ddigests || dest.dranges[q].off > dest.cap || dest.dranges[q].len > dest.cap - dest.dranges[q].off) return XLZ_ERR_BAD_ARG;
     if (dest.cap) {
         const int ok = device_dst_ok(ctx, dest.d_dst, dest.cap);
         if (ok != XLZ_OK) return ok;
@@ -3240,8 +3553,18 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         }
         if (st == XLZ_OK) {
             xlz_pack_stats pk = {};
-            st = batch_pack_run(b, items.data(), n, dest.d_dst, nullptr, stream, pk);
+            st = batch_pack_run(b, items.data(), items.size(), dest.d_dst, nullptr, stream, pk);
             if (st == XLZ_OK) publish_pack(ctx, pk);
+        }
+        if (st == XLZ_OK && dest.n_bcj2) { // the BCJ2 folders: merged into the destination, then checked THERE
+            xlz_bcj2_stats bj = {};
+            st = batch_bcj2_run(b, dest.bcj2, dest.n_bcj2, dest.d_dst, dest.bcj2_res, stream, dest.bcj2_mode == 2 ? 2 : 1, bj);
+            if (st == XLZ_OK) publish_bcj2(ctx, bj, true);
+            if (st == XLZ_OK && dest.n_dranges) {
+                xlz_check_stats chk = {};
+                st = dest_checks_run(b, dest.d_dst, dest.dranges, dest.n_dranges, dest.ddigests, stream, chk);
+                if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_check, chk, true);
+            }
         }
     }
     if (hipSetDevice(ctx->device) != hipSuccess) st = st == XLZ_OK ? XLZ_ERR_DEVICE : st;
