@@ -18,7 +18,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "../../include/xlz.h"
@@ -555,35 +554,82 @@ int place_folders(const Streams &s, size_t file_len, std::vector<xlz_7z_folder> 
     return XLZ_OK;
 }
 
-// decode the given folders (all of a StreamsInfo) into `out`, verify their CRCs
-int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_folder> &fo,
-                   const std::vector<xlz_7z_substream> &subs, uint8_t *out, int verify, size_t *unverified,
-                   xlz_ctx *const *ctxs = nullptr, size_t n_ctx = 0, // ctxs: deal the folders to several GPUs (xlz_decode_batch_multi)
-                   const std::vector<Folder> *chains = nullptr,      // filter mode 1: the folders' filter steps (Folder::steps)
-                   void *d_out = nullptr, size_t d_cap = 0,          // the device-destination form (xlz_7z_decode_device; out == NULL)
-                   const std::vector<xlz_7z_bcj2> *brecs = nullptr, int bcj2_mode = 0) // bcj2 mode 1 / 2 (d_out only): the BCJ2 folders' records
+// fn(off, len, crc) for every file of the folder that carries a CRC, in the folder's order (off: inside the folder's
+// bytes), then for the folder itself if it carries one.  -> how many that were
+template <class Fn> size_t each_crc(const xlz_7z_folder &f, const std::vector<xlz_7z_substream> &subs, Fn &&fn)
 {
-    std::vector<xlz_filter_step> fs;
-    std::vector<DeviceCopy> copies; // d_out: the Copy folders go up from the file as they are
-    std::vector<uint64_t> want_out, dst_off;
+    size_t n = 0;
+    uint64_t o = 0;
+    for (uint32_t j = 0; j < f.n_substreams; j++) {
+        const xlz_7z_substream &ss = subs[f.first_substream + j];
+        if (ss.has_crc) fn(o, ss.size, ss.crc), n++;
+        o += ss.size;
+    }
+    if (f.has_crc) fn((uint64_t)0, f.unpack_len, f.crc), n++;
+    return n;
+}
+
+// what a call of decode_folders is asked for
+struct FolderOpts {
+    uint8_t *out = nullptr; // the host destination, or ...
+    void *d_out = nullptr;  // ... the device destination of d_cap bytes (xlz_7z_decode_device)
+    size_t d_cap = 0;
+    int verify = 0;
+    size_t *unverified = nullptr;
+    const std::vector<Folder> *chains = nullptr;    // filter mode 1: the folders' filter steps (Folder::steps)
+    const std::vector<xlz_7z_bcj2> *brecs = nullptr; // bcj2 mode 1 / 2 (d_out only): the BCJ2 folders' records
+    int bcj2_mode = 0;
+};
+
+// The folders as one batch.  LZMA / LZMA2 folders are streams (which[k]: stream k's folder); a BCJ2 folder's LZMA / LZMA2
+// sub-streams are further streams (no_pack: not packed) and the folder an item that is merged into the device destination
+// behind the pack; Copy folders go to the destination from the file as they are.  dev_checks: cr[first[i] ...] = the
+// CRC32 ranges of folder i in each_crc's order, over its stream or -- a BCJ2 folder -- over the destination.
+struct FolderPlan {
     std::vector<xlz_stream_desc> d;
     std::vector<size_t> which;
-    // BCJ2 folders: their LZMA / LZMA2 sub-streams are further streams of the one batch (no_pack: not packed), the folders
-    // are merged into d_out behind the pack, and their CRCs are taken over the destination (ddg[ddg_first[i] ...] = folder
-    // i's files that carry a CRC, then the folder's own)
     std::vector<uint8_t> no_pack;
+    std::vector<uint64_t> want_out, dst_off;
+    std::vector<xlz_filter_step> fs;
+    std::vector<DeviceCopy> copies;
     std::vector<xlz_bcj2_item> bitems;
-    std::vector<DestRange> dranges;
-    std::vector<size_t> ddg_first(fo.size(), 0);
+    std::vector<xlz_check_range> cr;
+    std::vector<size_t> first;
+};
+int plan_folders(const uint8_t *file, const std::vector<xlz_7z_folder> &fo, const std::vector<xlz_7z_substream> &subs, const FolderOpts &o,
+                 bool dev_checks, FolderPlan &p)
+{
     size_t next_rec = 0;
-    uint8_t propbuf[5];
-    (void)propbuf;
+    p.first.assign(fo.size(), 0);
+    auto add_stream = [&](size_t folder, uint32_t method, uint64_t pack_off, uint64_t pack_len, uint64_t unpack_len, uint8_t props,
+                          uint32_t dict_size, bool packed, uint64_t dst) {
+        xlz_stream_desc s;
+        memset(&s, 0, sizeof s);
+        s.in = file + pack_off, s.in_len = (size_t)pack_len, s.out_cap = (size_t)unpack_len;
+        s.out = packed && !o.d_out ? o.out + dst : nullptr;
+        s.dict_size = dict_size; // (the batch engine applies DecodeDictSize's 4096 floor)
+        if (method == XLZ_7Z_LZMA) // NewLZMADecompressorForSevenZip(props, unpackSize, readers), reader1.go:32-61
+            s.format = XLZ_FMT_LZMA_RAW, s.props = props, s.unpack_size = unpack_len;
+        else // NewLZMA2DecompressorForSevenZip(props, _, readers), reader2.go:49-75
+            s.format = XLZ_FMT_LZMA2_RAW;
+        p.d.push_back(s), p.which.push_back(folder), p.no_pack.push_back(!packed);
+        p.want_out.push_back(unpack_len), p.dst_off.push_back(dst);
+    };
     for (size_t i = 0; i < fo.size(); i++) {
         const xlz_7z_folder &f = fo[i];
+        xlz_check_range c;
+        memset(&c, 0, sizeof c);
+        c.stream = p.d.size(), c.kind = XLZ_CHECK_CRC32;
+        uint64_t c_base = 0; // where the folder's bytes begin in what c.stream names
         if (f.method == XLZ_7Z_UNSUPPORTED) return XLZ_ERR_UNSUPPORTED;
+        if (f.method == XLZ_7Z_COPY) {
+            if (f.pack_len != f.unpack_len) return XLZ_ERR_RESULT;
+            p.copies.push_back(DeviceCopy{f.unpack_off, file + f.pack_off, f.unpack_len});
+            continue; // (its CRCs are the host's)
+        }
         if (f.method == XLZ_7Z_BCJ2) {
-            if (!d_out || !brecs || next_rec >= brecs->size() || (*brecs)[next_rec].folder != i) return XLZ_ERR_UNSUPPORTED;
-            const xlz_7z_bcj2 &rec = (*brecs)[next_rec++];
+            if (!o.d_out || !o.brecs || next_rec >= o.brecs->size() || (*o.brecs)[next_rec].folder != i) return XLZ_ERR_UNSUPPORTED;
+            const xlz_7z_bcj2 &rec = (*o.brecs)[next_rec++];
             if (f.unpack_len > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED; // (a folder of 4 GiB or more)
             xlz_bcj2_item it;
             memset(&it, 0, sizeof it);
@@ -594,177 +640,99 @@ int decode_folders(xlz_ctx *ctx, const uint8_t *file, const std::vector<xlz_7z_f
                     src[j]->stream = XLZ_BCJ2_RAW, src[j]->raw = file + sub[j]->pack_off, src[j]->raw_len = sub[j]->pack_len;
                     continue;
                 }
-                xlz_stream_desc s;
-                memset(&s, 0, sizeof s);
-                s.in = file + sub[j]->pack_off, s.in_len = (size_t)sub[j]->pack_len, s.out_cap = (size_t)sub[j]->unpack_len;
-                s.dict_size = sub[j]->dict_size;
-                if (sub[j]->method == XLZ_7Z_LZMA)
-                    s.format = XLZ_FMT_LZMA_RAW, s.props = sub[j]->props, s.unpack_size = sub[j]->unpack_len;
-                else
-                    s.format = XLZ_FMT_LZMA2_RAW;
-                src[j]->stream = d.size();
-                d.push_back(s), which.push_back(i), no_pack.push_back(1);
-                want_out.push_back(sub[j]->unpack_len), dst_off.push_back(0);
+                src[j]->stream = p.d.size();
+                add_stream(i, sub[j]->method, sub[j]->pack_off, sub[j]->pack_len, sub[j]->unpack_len, sub[j]->props, sub[j]->dict_size, false, 0);
             }
             it.rc = file + rec.rc_off, it.rc_len = rec.rc_len, it.out_len = f.unpack_len, it.dst_off = f.unpack_off;
-            bitems.push_back(it);
-            if (verify) {
-                ddg_first[i] = dranges.size();
-                uint64_t o = 0;
-                for (uint32_t j = 0; j < f.n_substreams; j++) {
-                    const xlz_7z_substream &ss = subs[f.first_substream + j];
-                    if (ss.has_crc) dranges.push_back(DestRange{f.unpack_off + o, ss.size});
-                    o += ss.size;
+            p.bitems.push_back(it);
+            c.stream = xlzpost::kDestStream, c_base = f.unpack_off; // (the merged bytes never sit in the arena)
+        } else {
+            if (o.chains && (*o.chains)[i].chain)
+                for (const auto &stp : (*o.chains)[i].steps) {
+                    xlz_filter_step q;
+                    memset(&q, 0, sizeof q);
+                    q.stream = p.d.size(), q.id = stp.first, q.param = stp.second;
+                    p.fs.push_back(q);
                 }
-                if (f.has_crc) dranges.push_back(DestRange{f.unpack_off, f.unpack_len});
-            }
-            continue;
+            add_stream(i, f.method, f.pack_off, f.pack_len, f.unpack_len, f.props, f.dict_size, true, f.unpack_off);
         }
-        if (f.method == XLZ_7Z_COPY) {
-            if (f.pack_len != f.unpack_len) return XLZ_ERR_RESULT;
-            if (d_out)
-                copies.push_back(DeviceCopy{f.unpack_off, file + f.pack_off, f.unpack_len});
-            else
-                memcpy(out + f.unpack_off, file + f.pack_off, (size_t)f.unpack_len);
-            continue;
-        }
-        xlz_stream_desc s;
-        memset(&s, 0, sizeof s);
-        s.in = file + f.pack_off;
-        s.in_len = (size_t)f.pack_len;
-        s.out = d_out ? nullptr : out + f.unpack_off;
-        s.out_cap = (size_t)f.unpack_len;
-        if (f.method == XLZ_7Z_LZMA) { // NewLZMADecompressorForSevenZip(props, unpackSize, readers), reader1.go:32-61
-            s.format = XLZ_FMT_LZMA_RAW;
-            s.props = f.props;
-            s.dict_size = f.dict_size; // (the batch engine applies DecodeDictSize's 4096 floor)
-            s.unpack_size = f.unpack_len;
-        } else { // NewLZMA2DecompressorForSevenZip(props, _, readers), reader2.go:49-75
-            s.format = XLZ_FMT_LZMA2_RAW;
-            s.dict_size = f.dict_size;
-        }
-        if (chains && (*chains)[i].chain)
-            for (const auto &stp : (*chains)[i].steps) {
-                xlz_filter_step q;
-                memset(&q, 0, sizeof q);
-                q.stream = d.size(), q.id = stp.first, q.param = stp.second;
-                fs.push_back(q);
-            }
-        d.push_back(s);
-        which.push_back(i), no_pack.push_back(0);
-        want_out.push_back(f.unpack_len), dst_off.push_back(f.unpack_off);
+        p.first[i] = p.cr.size();
+        if (dev_checks)
+            each_crc(f, subs, [&](uint64_t off, uint64_t len, uint32_t) {
+                c.off = c_base + off, c.len = len;
+                p.cr.push_back(c);
+            });
     }
-    std::vector<xlz_result> r(d.size());
-    std::vector<xlz_bcj2_result> bres(bitems.size());
-    std::vector<uint64_t> ddg(dranges.size());
-    DeviceDest dest;
-    dest.no_pack = no_pack.data(), dest.bcj2 = bitems.data(), dest.n_bcj2 = bitems.size(), dest.bcj2_res = bres.data(), dest.bcj2_mode = bcj2_mode;
-    dest.dranges = dranges.data(), dest.n_dranges = dranges.size(), dest.ddigests = ddg.data();
-    dest.d_dst = d_out, dest.cap = d_cap, dest.want_out = want_out.data(), dest.dst_off = dst_off.data();
-    dest.copies = copies.data(), dest.n_copies = copies.size();
-    // (a device destination: one batch with what `w` asks for behind it, the pack and the Copy folders' upload)
-    auto decode = [&](const PostWork &w) {
-        return d_out ? xlz_internal_decode_device(ctx, d.data(), d.size(), r.data(), w, dest) : xlz_internal_decode_batch(ctx, d.data(), d.size(), r.data(), w);
-    };
+    return XLZ_OK;
+}
+
+// decode the given folders (all of a StreamsInfo) into o.out or o.d_out, verify their CRCs.  ctxs[0] runs the batch; more
+// than one context: the folders are dealt to several GPUs (xlz_decode_batch_multi)
+int decode_folders(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, const std::vector<xlz_7z_folder> &fo,
+                   const std::vector<xlz_7z_substream> &subs, const FolderOpts &o)
+{
+    xlz_ctx *ctx = ctxs[0];
     // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 of every file and folder that the batch decodes comes
-    // from the device with the batch's results -- per-file ranges inside solid folders --, in the order the loop below
-    // asks for them: dg[dg_first[i] ...] = folder i's files that carry a CRC, then the folder's own
+    // from the device with the batch's results -- per-file ranges inside solid folders
     // (a device destination: there are no bytes on the host to check, so always)
-    const bool dev = verify && n_ctx <= 1 && ctx && (d_out || xlz_ctx_check_mode(ctx) >= 1);
-    std::vector<uint64_t> dg;
-    std::vector<size_t> dg_first(fo.size(), 0);
-    if (dev) {
-        std::vector<xlz_check_range> cr;
-        for (size_t k = 0; k < which.size(); k++) {
-            if (no_pack[k]) continue; // (a BCJ2 folder's sub-stream: the folder is checked in the destination)
-            const xlz_7z_folder &f = fo[which[k]];
-            dg_first[which[k]] = cr.size();
-            xlz_check_range c;
-            memset(&c, 0, sizeof c);
-            c.stream = k, c.kind = XLZ_CHECK_CRC32;
-            uint64_t o = 0;
-            for (uint32_t j = 0; j < f.n_substreams; j++) {
-                const xlz_7z_substream &ss = subs[f.first_substream + j];
-                if (ss.has_crc) {
-                    c.off = o, c.len = ss.size;
-                    cr.push_back(c);
-                }
-                o += ss.size;
-            }
-            if (f.has_crc) {
-                c.off = 0, c.len = f.unpack_len;
-                cr.push_back(c);
-            }
-        }
-        dg.resize(cr.size());
-        if (!d.empty() || d_out) {
-            int st = decode(PostWork{fs.data(), fs.size(), cr.data(), cr.size(), dg.data(), nullptr, true});
-            if (st != XLZ_OK) return st;
-        }
-    } else if (!fs.empty() || d_out) { // (CRCs, if asked for, on host threads below: over the filtered bytes)
-        int st = decode(PostWork{fs.data(), fs.size(), nullptr, 0, nullptr, nullptr, true});
-        if (st != XLZ_OK) return st;
-    } else if (!d.empty()) {
-        int st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, d.data(), d.size(), r.data())
-                           : xlz_decode_batch(ctx, d.data(), d.size(), r.data());
-        if (st != XLZ_OK) return st;
-    }
-    for (size_t k = 0; k < d.size(); k++) {
+    const bool dev = o.verify && n_ctx <= 1 && ctx && (o.d_out || xlz_ctx_check_mode(ctx) >= 1);
+    FolderPlan p;
+    int st = plan_folders(file, fo, subs, o, dev, p);
+    if (st != XLZ_OK) return st;
+    // run: the host batch, the multi-GPU batch, or (a device destination) one batch with the pack, the merges and the
+    // Copy folders' upload behind it
+    std::vector<xlz_result> r(p.d.size());
+    std::vector<xlz_bcj2_result> bres(p.bitems.size());
+    std::vector<uint64_t> dg(p.cr.size());
+    if (!o.d_out)
+        for (const DeviceCopy &c : p.copies) memcpy(o.out + c.dst_off, c.src, (size_t)c.len);
+    if (dev || !p.fs.empty() || o.d_out) { // (without dev the CRCs, if asked for, on host threads below: over the filtered bytes)
+        const PostWork w = {p.fs.data(), p.fs.size(), p.cr.data(), p.cr.size(), dg.data(), nullptr, true};
+        if (o.d_out) {
+            DeviceDest dest;
+            dest.d_dst = o.d_out, dest.cap = o.d_cap, dest.want_out = p.want_out.data(), dest.dst_off = p.dst_off.data();
+            dest.copies = p.copies.data(), dest.n_copies = p.copies.size(), dest.no_pack = p.no_pack.data();
+            dest.bcj2 = p.bitems.data(), dest.n_bcj2 = p.bitems.size(), dest.bcj2_res = bres.data(), dest.bcj2_mode = o.bcj2_mode;
+            st = xlz_internal_decode_device(ctx, p.d.data(), p.d.size(), r.data(), w, dest);
+        } else if (!p.d.empty())
+            st = xlz_internal_decode_batch(ctx, p.d.data(), p.d.size(), r.data(), w);
+    } else if (!p.d.empty())
+        st = n_ctx > 1 ? xlz_decode_batch_multi(ctxs, n_ctx, p.d.data(), p.d.size(), r.data())
+                       : xlz_decode_batch(ctx, p.d.data(), p.d.size(), r.data());
+    if (st != XLZ_OK) return st;
+    for (size_t k = 0; k < p.d.size(); k++) {
         if (r[k].status < 0) return r[k].status;
-        if (r[k].out_len != want_out[k]) return XLZ_ERR_RESULT; // a folder (a BCJ2 folder's stream) decodes to exactly its size
+        if (r[k].out_len != p.want_out[k]) return XLZ_ERR_RESULT; // a folder (a BCJ2 folder's stream) decodes to exactly its size
     }
     for (const xlz_bcj2_result &q : bres)
         if (q.status < 0) return q.status == XLZ_ERR_UNSUPPORTED ? XLZ_ERR_UNSUPPORTED : XLZ_ERR_RESULT; // a merge that failed
-    if (verify) {
-        size_t nu = 0;
-        std::vector<int> bad(fo.size(), 0);
-        const unsigned hw = std::thread::hardware_concurrency();
-        const unsigned nth = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min<unsigned>(hw ? hw : 1, 16), fo.size()));
-        auto work = [&](unsigned t) {
-            for (size_t i = t; i < fo.size(); i += nth) {
-                const xlz_7z_folder &f = fo[i];
-                // what the host reads of the folder: its bytes in the caller's buffer, or (a device destination, where only
-                // Copy folders are the host's) in the file
-                const uint8_t *fb = d_out ? file + f.pack_off : out + f.unpack_off;
-                uint64_t o = 0;
-                bool any = false;
-                const bool on_dev = dev && f.method != XLZ_7Z_COPY; // (Copy folders never were on the device)
-                const bool on_dst = f.method == XLZ_7Z_BCJ2;        // (merged into the destination and checked there)
-                size_t q = on_dst ? ddg_first[i] : dg_first[i];
-                const std::vector<uint64_t> &dgs = on_dst ? ddg : dg;
-                for (uint32_t k = 0; k < f.n_substreams; k++) {
-                    const xlz_7z_substream &ss = subs[f.first_substream + k];
-                    if (ss.has_crc) {
-                        any = true;
-                        if ((on_dev ? (uint32_t)dgs[q++] : xlzcheck::crc32(fb + o, (size_t)ss.size)) != ss.crc) bad[i] = 1;
-                    }
-                    o += ss.size;
-                }
-                if (f.has_crc) {
-                    any = true;
-                    if ((on_dev ? (uint32_t)dgs[q++] : xlzcheck::crc32(fb, (size_t)f.unpack_len)) != f.crc) bad[i] = 1;
-                }
-                if (!any && !bad[i]) bad[i] = 2;
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nth; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
-        if (dev)
-            for (const xlz_7z_folder &f : fo) {
-                if (f.method != XLZ_7Z_COPY) continue;
-                uint64_t nr = f.has_crc, nbytes = f.has_crc ? f.unpack_len : 0;
-                for (uint32_t k = 0; k < f.n_substreams; k++)
-                    if (subs[f.first_substream + k].has_crc) nr++, nbytes += subs[f.first_substream + k].size;
-                if (nr) xlz_internal_check_stats_host(ctx, nr, nbytes);
-            }
-        for (int b : bad) {
-            if (b == 1) return XLZ_ERR_RESULT;
-            nu += b == 2;
+    if (!o.verify) return XLZ_OK;
+    // verify: every CRC against the device's digest, or against the host's over the folder's bytes -- in the caller's
+    // buffer, or (a device destination, where only Copy folders are the host's) in the file
+    std::vector<int> bad(fo.size(), 0); // 1: a CRC differs, 2: there was none
+    xlzpost::parallel_for(fo.size(), xlzpost::host_thread_cap(16), [&](size_t i) {
+        const xlz_7z_folder &f = fo[i];
+        const uint8_t *fb = o.d_out ? file + f.pack_off : o.out + f.unpack_off;
+        const bool on_dev = dev && f.method != XLZ_7Z_COPY; // (Copy folders never were on the device)
+        size_t q = p.first[i];
+        bool differs = false;
+        const size_t n = each_crc(f, subs, [&](uint64_t off, uint64_t len, uint32_t crc) {
+            if ((on_dev ? (uint32_t)dg[q++] : xlzcheck::crc32(fb + off, (size_t)len)) != crc) differs = true;
+        });
+        bad[i] = differs ? 1 : n ? 0 : 2;
+    });
+    for (size_t i = 0; i < fo.size() && dev; i++) // (the Copy folders' CRCs were the host's)
+        if (fo[i].method == XLZ_7Z_COPY) {
+            uint64_t nbytes = 0;
+            const size_t nr = each_crc(fo[i], subs, [&](uint64_t, uint64_t len, uint32_t) { nbytes += len; });
+            if (nr) xlz_internal_check_stats_host(ctx, nr, nbytes);
         }
-        if (unverified) *unverified = nu;
+    size_t nu = 0;
+    for (size_t i = 0; i < fo.size(); i++) {
+        if (bad[i] == 1) return XLZ_ERR_RESULT;
+        nu += bad[i] == 2;
     }
+    if (o.unverified) *o.unverified = nu;
     return XLZ_OK;
 }
 
@@ -806,7 +774,9 @@ int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std:
             if (fo[0].unpack_len > (256u << 20)) return XLZ_ERR_UNSUPPORTED;
             if (!ctx && fo[0].method != XLZ_7Z_COPY) return XLZ_ERR_DEVICE; // decoding the header needs the GPU
             std::vector<uint8_t> next((size_t)fo[0].unpack_len + 1);
-            st = decode_folders(ctx, file, fo, es.subs, next.data(), 1, nullptr);
+            FolderOpts o;
+            o.out = next.data(), o.verify = 1;
+            st = decode_folders(&ctx, 1, file, fo, es.subs, o);
             if (st != XLZ_OK) return st;
             next.resize((size_t)fo[0].unpack_len);
             decoded_header.swap(next);
@@ -1006,26 +976,23 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     uint64_t total = 0;
     for (auto &f : fo) total += f.unpack_len;
     if (total > out_cap) return XLZ_ERR_OUT_CAP;
-    if (!brecs.empty()) {
-        // an archive that HAS a BCJ2 folder: the device-destination path -- for a host destination into a block from the
-        // context's pool, followed by one download
-        for (auto &f : fo)
-            if (f.method == XLZ_7Z_UNSUPPORTED) return XLZ_ERR_UNSUPPORTED;
-        void *blk = nullptr;
-        if (!d_out) {
-            st = xlz_internal_device_block(ctx, (size_t)total, &blk);
-            if (st != XLZ_OK) return st;
-            if (verify) xlz_internal_check_stats_reset(ctx);
-        }
-        st = decode_folders(ctx, file, fo, s.subs, nullptr, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr, d_out ? d_out : blk,
-                            d_out ? out_cap : (size_t)total, &brecs, bmode);
-        if (st == XLZ_OK && blk) st = xlz_internal_device_block_download(ctx, blk, out, (size_t)total);
-        xlz_internal_device_block_release(ctx, blk);
+    FolderOpts o;
+    o.out = out, o.d_out = d_out, o.d_cap = out_cap, o.verify = verify, o.unverified = unverified;
+    o.chains = chains ? &s.folders : nullptr, o.brecs = &brecs, o.bcj2_mode = bmode;
+    // an archive that HAS a BCJ2 folder: the device-destination path -- for a host destination into a block from the
+    // context's pool, followed by one download
+    void *blk = nullptr;
+    for (auto &f : fo)
+        if (!brecs.empty() && f.method == XLZ_7Z_UNSUPPORTED) return XLZ_ERR_UNSUPPORTED;
+    if (!brecs.empty() && !d_out) {
+        st = xlz_internal_device_block(ctx, (size_t)total, &blk);
         if (st != XLZ_OK) return st;
-        *out_len = total;
-        return XLZ_OK;
+        if (verify) xlz_internal_check_stats_reset(ctx);
+        o.out = nullptr, o.d_out = blk, o.d_cap = (size_t)total;
     }
-    st = decode_folders(ctx, file, fo, s.subs, out, verify, unverified, ctxs, n_ctx, chains ? &s.folders : nullptr, d_out, out_cap);
+    st = decode_folders(ctxs, n_ctx, file, fo, s.subs, o);
+    if (st == XLZ_OK && blk) st = xlz_internal_device_block_download(ctx, blk, out, (size_t)total);
+    xlz_internal_device_block_release(ctx, blk);
     if (st != XLZ_OK) return st;
     *out_len = total;
     return XLZ_OK;

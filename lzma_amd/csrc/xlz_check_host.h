@@ -22,9 +22,6 @@ struct DeviceCopy {
     const uint8_t *src;
     uint64_t len;
 };
-struct DestRange { // bytes of the destination, for a CRC32 over them
-    uint64_t off, len;
-};
 struct DeviceDest {
     void *d_dst = nullptr;
     size_t cap = 0;
@@ -33,16 +30,12 @@ struct DeviceDest {
     size_t n_copies = 0;
     // .7z BCJ2 folders (bcj2 mode 1 / 2): no_pack[i] != 0 -- stream i is a sub-stream of one, it must still produce
     // want_out[i] bytes but is not packed; the folders are merged into d_dst behind the pack (items as xlz_batch_bcj2 takes
-    // them, bcj2_res[] their outcomes, bcj2_mode 1: on the device, 2: on host threads), and the CRC32 of dranges[] of the
-    // DESTINATION -- the merged bytes never sit in the arena -- goes to ddigests[]
+    // them, bcj2_res[] their outcomes, bcj2_mode 1: on the device, 2: on host threads)
     const uint8_t *no_pack = nullptr;
     const xlz_bcj2_item *bcj2 = nullptr;
     size_t n_bcj2 = 0;
     xlz_bcj2_result *bcj2_res = nullptr;
     int bcj2_mode = 1;
-    const DestRange *dranges = nullptr;
-    size_t n_dranges = 0;
-    uint64_t *ddigests = nullptr;
 };
 // a device block of at least `bytes` from the context's pool (xlz_7z_decode with a BCJ2 folder decodes into one), its
 // download into host memory once the context's stream has drained, and its return
@@ -51,8 +44,11 @@ int xlz_internal_device_block_download(xlz_ctx *ctx, const void *p, uint8_t *dst
 void xlz_internal_device_block_release(xlz_ctx *ctx, void *p);
 void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx);
 // The device-destination form of xlz_internal_decode_batch (streams[i].out is NULL): one batch -- create, run, results,
-// the size checks above (a stream's own failure, then XLZ_ERR_RESULT), post.steps, post.ranges (exactly one of crc_out /
-// digest_out when there are ranges; the statistics always accumulate), the pack into dest, the copies, and a wait for
-// the context's stream.  XLZ_ERR_UNSUPPORTED for a stream of 4 GiB and more.
+// the size checks above (a stream's own failure, then XLZ_ERR_RESULT) -- and behind it, all on the context's stream:
+// post.steps; the digests of post.ranges that name a stream; the pack into dest; the BCJ2 merges; the digests of
+// post.ranges that name the destination; the copies; a wait.  post.ranges is ONE list (exactly one of crc_out / digest_out
+// when it is not empty, indexed like it): a range whose stream is xlzpost::kDestStream means bytes [off, off + len) of
+// d_dst -- where alone a merged BCJ2 folder ever lies; CRC32 / CRC64, inside dest.cap.  The statistics always
+// accumulate, but the pack's, which are this call's.  XLZ_ERR_UNSUPPORTED for a stream of 4 GiB and more.
 int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
                                const DeviceDest &dest);

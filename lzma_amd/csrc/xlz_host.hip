@@ -438,19 +438,6 @@ unsigned host_threads(size_t bytes)
     return want < cap ? want : cap;
 }
 
-template <class F> void run_threads(unsigned n, F &&f)
-{
-    if (n <= 1) {
-        f(0u);
-        return;
-    }
-    std::vector<std::thread> th;
-    th.reserve(n - 1);
-    for (unsigned t = 1; t < n; t++) th.emplace_back([&f, t] { f(t); });
-    f(0u);
-    for (auto &x : th) x.join();
-}
-
 } // namespace
 
 extern "C" int xlz_ctx_create(int device, xlz_ctx **out)
@@ -909,7 +896,7 @@ template <class At> int pack_upload(xlz_ctx *ctx, uint8_t *stage, uint8_t *dst, 
         return k + 1 < n ? at(k + 1).off : total;
     };
     const unsigned nth = host_threads((size_t)total);
-    run_threads(nth, [&](unsigned t) {
+    xlzpost::parallel_for(nth, nth, [&](size_t t) {
         (void)hipSetDevice(ctx->device);
         const size_t k0 = n * t / nth, k1 = n * (t + 1) / nth;
         if (k0 >= k1) return;
@@ -1721,11 +1708,12 @@ int check_tables(xlz_ctx *ctx)
     return XLZ_OK;
 }
 
-int check_args(const xlz_check_range *ranges, size_t n_ranges, size_t n_streams, const void *digests, bool sha_too = false)
+// dest_too: ranges of a device destination (xlzpost::kDestStream) pass; only xlz_internal_decode_device takes them
+int check_args(const xlz_check_range *ranges, size_t n_ranges, size_t n_streams, const void *digests, bool sha_too = false, bool dest_too = false)
 {
     if ((!ranges || !digests) && n_ranges) return XLZ_ERR_BAD_ARG;
     for (size_t q = 0; q < n_ranges; q++)
-        if (ranges[q].stream >= n_streams ||
+        if ((ranges[q].stream >= n_streams && !(dest_too && ranges[q].stream == xlzpost::kDestStream)) ||
             (ranges[q].kind != XLZ_CHECK_CRC32 && ranges[q].kind != XLZ_CHECK_CRC64 && !(sha_too && ranges[q].kind == XLZ_CHECK_SHA256)) ||
             ranges[q].reserved)
             return XLZ_ERR_BAD_ARG;
@@ -1765,49 +1753,35 @@ int timed_bracket(hipStream_t stream, PostScratch &s, const char *what, float *m
     return XLZ_OK;
 }
 
-// The digests of ranges[idx[0 .. n_idx)] (idx == nullptr: of ranges[0 .. n_idx)) of a COLLECTED batch, whose stream
-// `stream_base` is the batch's first: the ranges of streams in the output arena by the check kernels, queued on `stream`
-// -- the batch's own, or any other: collect() has waited for everything that writes the arena, its re-runs included --
-// and waited for.  digests[] is indexed like ranges[].  Streams marked oversize are skipped (xlz_decode_batch settles them
-// behind its batches); other streams outside the arena are checked on the host over `streams` (the batch's descriptors)
-// when given.
-int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *idx, size_t n_idx, size_t stream_base, uint64_t *digests,
-                     hipStream_t stream, const xlz_stream_desc *streams, xlz_check_stats &acc)
+// One run of the check kernels: the CRC of e.len bytes at base + e.off -> digests[e.out] for every entry (no entry is
+// empty), CRC32 and CRC64 in one launch each, queued on `stream` and waited for.  `base` is aligned to 16 and holds `limit`
+// bytes; XLZ_ERR_UNSUPPORTED for an entry that leaves them or for more segments than a launch can count.
+struct CheckEntry {
+    uint64_t off, len;
+    uint32_t kind; // XLZ_CHECK_CRC32 / XLZ_CHECK_CRC64
+    size_t out;
+};
+int check_table_run(xlz_batch *b, const uint8_t *base, uint64_t limit, const std::vector<CheckEntry> &entries, uint64_t *digests,
+                    hipStream_t stream, xlz_check_stats &acc)
 {
     using xlzchk::DevRange;
-    using xlzpost::Place;
-    if (!n_idx) return XLZ_OK;
-    std::vector<DevRange> dev[2]; // CRC32, CRC64
-    std::vector<size_t> where[2]; // ... and the index of each one's digest
-    uint64_t segs[2] = {0, 0}, dev_bytes = 0;
-    for (size_t q = 0; q < n_idx; q++) {
-        const size_t ri = idx ? idx[q] : q;
-        const xlz_check_range &r = ranges[ri];
-        const size_t s = (size_t)(r.stream - stream_base);
-        const xlzpost::Clip c = xlzpost::clip(stream_out(b, s, streams), r.off, r.len);
-        if (c.place == Place::Oversize || r.kind == XLZ_CHECK_SHA256) continue; // (SHA-256: batch_sha256_run)
-        digests[ri] = 0;
-        if (c.place == Place::Empty) {
-            acc.empty_ranges++;
-        } else if (c.place == Place::Caller) {
-            digests[ri] = host_digest(r.kind, streams[s].out + c.lo, c.hi - c.lo);
-            acc.host_ranges++, acc.host_bytes += c.hi - c.lo;
-        } else {
-            const int k = r.kind == XLZ_CHECK_CRC64;
-            DevRange d;
-            d.off = b->plans[s].out_off + c.lo, d.len = c.hi - c.lo;
-            const uint64_t ns = xlzchk::range_segments(d.off, d.len);
-            if (d.off + d.len > b->out_bytes || segs[k] + ns > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
-            d.seg_first = (uint32_t)segs[k], d.n_segs = (uint32_t)ns, d.out_index = (uint32_t)where[0].size() + (uint32_t)where[1].size(), d.reserved = 0;
-            segs[k] += ns;
-            dev[k].push_back(d);
-            where[k].push_back(ri);
-            dev_bytes += d.len;
-        }
-    }
-    const size_t n_dev = dev[0].size() + dev[1].size();
+    const size_t n_dev = entries.size();
     if (!n_dev) return XLZ_OK;
     if (n_dev > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+    std::vector<DevRange> tab(n_dev); // the CRC32 ranges, then the CRC64 ranges
+    size_t n32 = 0, at[2] = {0, 0};
+    for (const CheckEntry &e : entries) n32 += e.kind != XLZ_CHECK_CRC64;
+    at[1] = n32;
+    uint64_t segs[2] = {0, 0}, dev_bytes = 0;
+    for (size_t j = 0; j < n_dev; j++) {
+        const CheckEntry &e = entries[j];
+        const int k = e.kind == XLZ_CHECK_CRC64;
+        const uint64_t ns = xlzchk::range_segments(e.off, e.len);
+        if (e.off > limit || e.len > limit - e.off || segs[k] + ns > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+        DevRange &d = tab[at[k]++];
+        d.off = e.off, d.len = e.len, d.seg_first = (uint32_t)segs[k], d.n_segs = (uint32_t)ns, d.out_index = (uint32_t)j, d.reserved = 0;
+        segs[k] += ns, dev_bytes += e.len;
+    }
     xlz_ctx *ctx = b->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1816,29 +1790,70 @@ int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *
     const size_t tab_bytes = n_dev * sizeof(DevRange), seg_bytes = (size_t)(segs[0] + segs[1]) * 8, dig_bytes = n_dev * 8;
     st = b->chk.reserve(b, tab_bytes + seg_bytes + dig_bytes, tab_bytes + dig_bytes);
     if (st != XLZ_OK) return st;
-    DevRange *h_tab = reinterpret_cast<DevRange *>(b->chk.pin);
-    uint64_t *h_dig = reinterpret_cast<uint64_t *>(b->chk.pin + tab_bytes);
-    if (!dev[0].empty()) memcpy(h_tab, dev[0].data(), dev[0].size() * sizeof(DevRange));
-    if (!dev[1].empty()) memcpy(h_tab + dev[0].size(), dev[1].data(), dev[1].size() * sizeof(DevRange));
+    memcpy(b->chk.pin, tab.data(), tab_bytes);
+    const uint64_t *h_dig = reinterpret_cast<const uint64_t *>(b->chk.pin + tab_bytes);
     DevRange *d_tab = reinterpret_cast<DevRange *>(b->chk.dev);
     uint64_t *d_seg = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes);
     uint64_t *d_dig = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes + seg_bytes);
-    HIP_TRY(hipMemcpyAsync(d_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_tab, b->chk.pin, tab_bytes, hipMemcpyHostToDevice, stream));
     float ms = 0;
     st = timed_bracket(
         stream, b->chk, "check kernels", &ms,
         [&] {
-            return xlz::check_launch(32, b->d_out, d_tab, (uint32_t)dev[0].size(), (uint32_t)segs[0], ctx->chk_tab[0], ctx->chk_consts[0], d_seg,
-                                     d_dig, ctx->num_cus, stream) == 0 &&
-                   xlz::check_launch(64, b->d_out, d_tab + dev[0].size(), (uint32_t)dev[1].size(), (uint32_t)segs[1], ctx->chk_tab[1],
-                                     ctx->chk_consts[1], d_seg + segs[0], d_dig, ctx->num_cus, stream) == 0;
+            return xlz::check_launch(32, base, d_tab, (uint32_t)n32, (uint32_t)segs[0], ctx->chk_tab[0], ctx->chk_consts[0], d_seg, d_dig,
+                                     ctx->num_cus, stream) == 0 &&
+                   xlz::check_launch(64, base, d_tab + n32, (uint32_t)(n_dev - n32), (uint32_t)segs[1], ctx->chk_tab[1], ctx->chk_consts[1],
+                                     d_seg + segs[0], d_dig, ctx->num_cus, stream) == 0;
         },
-        h_dig, d_dig, dig_bytes);
+        b->chk.pin + tab_bytes, d_dig, dig_bytes);
     if (st != XLZ_OK) return st;
-    for (int k = 0; k < 2; k++)
-        for (size_t j = 0; j < dev[k].size(); j++) digests[where[k][j]] = h_dig[dev[k][j].out_index];
+    for (size_t j = 0; j < n_dev; j++) digests[entries[j].out] = h_dig[j];
     acc.device_ranges += n_dev, acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches++;
     return XLZ_OK;
+}
+
+// The CRCs of ranges[idx[0 .. n_idx)] (idx == nullptr: of ranges[0 .. n_idx)) of a COLLECTED batch, whose stream
+// `stream_base` is the batch's first, by check_table_run on `stream` -- the batch's own, or any other: collect() has
+// waited for everything that writes the arena, its re-runs included.  digests[] is indexed like ranges[].  What is left to
+// this function is where a range's bytes lie.  dst == nullptr: in its stream's output -- in the arena; streams marked
+// oversize are skipped (xlz_decode_batch settles them behind its batches), other streams outside the arena are checked on
+// the host over `streams` (the batch's descriptors) when given.  dst: every range names bytes of that device destination
+// (xlzpost::kDestStream), which the kernels read from dst->d_dst rounded down to 16.
+int batch_checks_run(xlz_batch *b, const xlz_check_range *ranges, const size_t *idx, size_t n_idx, size_t stream_base, uint64_t *digests,
+                     hipStream_t stream, const xlz_stream_desc *streams, xlz_check_stats &acc, const DeviceDest *dst = nullptr)
+{
+    using xlzpost::Place;
+    const uint64_t mis = dst ? (uintptr_t)dst->d_dst & 15 : 0;
+    std::vector<CheckEntry> dev;
+    for (size_t q = 0; q < n_idx; q++) {
+        const size_t ri = idx ? idx[q] : q;
+        const xlz_check_range &r = ranges[ri];
+        if (r.kind == XLZ_CHECK_SHA256) continue; // (batch_sha256_run)
+        if (dst) {
+            uint64_t at;
+            if (!xlzpost::dest_resolve(r.off, r.len, dst->cap, mis, &at)) return XLZ_ERR_UNSUPPORTED;
+            digests[ri] = 0;
+            if (r.len)
+                dev.push_back(CheckEntry{at, r.len, r.kind, ri});
+            else
+                acc.empty_ranges++;
+            continue;
+        }
+        const size_t s = (size_t)(r.stream - stream_base);
+        const xlzpost::Clip c = xlzpost::clip(stream_out(b, s, streams), r.off, r.len);
+        if (c.place == Place::Oversize) continue;
+        digests[ri] = 0;
+        if (c.place == Place::Empty) {
+            acc.empty_ranges++;
+        } else if (c.place == Place::Caller) {
+            digests[ri] = host_digest(r.kind, streams[s].out + c.lo, c.hi - c.lo);
+            acc.host_ranges++, acc.host_bytes += c.hi - c.lo;
+        } else {
+            dev.push_back(CheckEntry{b->plans[s].out_off + c.lo, c.hi - c.lo, r.kind, ri});
+        }
+    }
+    if (dst) return check_table_run(b, static_cast<const uint8_t *>(dst->d_dst) - mis, dst->cap + mis, dev, digests, stream, acc);
+    return check_table_run(b, b->d_out, b->out_bytes, dev, digests, stream, acc);
 }
 
 // ---- SHA-256 (xlz_sha256_dev.hip) ----
@@ -1877,20 +1892,8 @@ struct ShaHostJob {
 };
 void sha256_host_jobs(const std::vector<ShaHostJob> &jobs)
 {
-    if (jobs.empty()) return;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const unsigned nth = (unsigned)std::min<size_t>(std::max(1u, std::min(hw ? hw : 1u, xlzsha::kHostThreads)), jobs.size());
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < jobs.size();) xlzcheck::sha256(jobs[i].p, (size_t)jobs[i].n, jobs[i].out->b);
-    };
-    std::vector<std::thread> th;
-    try {
-        for (unsigned t = 1; t < nth; t++) th.emplace_back(work);
-    } catch (...) { // (no thread to be had: this one does it all)
-    }
-    work();
-    for (auto &x : th) x.join();
+    xlzpost::parallel_for(jobs.size(), xlzpost::host_thread_cap(xlzsha::kHostThreads),
+                          [&](size_t i) { xlzcheck::sha256(jobs[i].p, (size_t)jobs[i].n, jobs[i].out->b); });
 }
 void sha256_of_nothing(xlz_digest *out) { xlzcheck::sha256(out->b, 0, out->b); }
 
@@ -2028,6 +2031,33 @@ void crc_digest(uint64_t v, xlz_digest *out)
     for (int k = 0; k < 8; k++) out->b[k] = (uint8_t)(v >> (8 * k));
 }
 
+// The digests of w.ranges[idx[..]] of a collected batch (idx, stream_base, stream, streams, dst: as batch_checks_run takes
+// them; `later`: as batch_sha256_run), the one sequence every caller runs: the CRC ranges, then -- the 32-byte form only
+// -- the SHA-256 ranges, and the CRCs put into that form.  chk and sha gain what was done; the SHA-256 ranges count in
+// chk too.
+int batch_digests_run(xlz_batch *b, const PostWork &w, const size_t *idx, size_t n_idx, size_t stream_base, hipStream_t stream,
+                      const xlz_stream_desc *streams, std::vector<ShaHostJob> *later, xlz_check_stats &chk, xlz_sha256_stats &sha,
+                      const DeviceDest *dst = nullptr)
+{
+    if (!n_idx) return XLZ_OK;
+    std::vector<uint64_t> crc_of(w.digest_out ? w.n_ranges : 0);
+    uint64_t *crc = w.digest_out ? crc_of.data() : w.crc_out;
+    xlz_check_stats c = {};
+    xlz_sha256_stats h = {};
+    int st = batch_checks_run(b, w.ranges, idx, n_idx, stream_base, crc, stream, streams, c, dst);
+    if (st == XLZ_OK && w.digest_out && !dst) // (it looks for the XLZ_CHECK_SHA256 ranges among them)
+        st = batch_sha256_run(b, w.ranges, idx, n_idx, stream_base, w.digest_out, stream, streams, later, h);
+    if (st != XLZ_OK) return st;
+    for (size_t q = 0; q < n_idx && w.digest_out; q++) {
+        const size_t ri = idx ? idx[q] : q;
+        if (w.ranges[ri].kind != XLZ_CHECK_SHA256) crc_digest(crc[ri], &w.digest_out[ri]);
+    }
+    xlzpost::stats_add(c, h);
+    xlzpost::stats_add(chk, c);
+    xlzpost::stats_add(sha, h, xlzpost::ThresholdIsMax{});
+    return XLZ_OK;
+}
+
 // What the xlz_batch_* calls of the post-decode kernels begin with: the batch has run, args(streams of the batch) accepts
 // the call's tables, the results are collected (nothing writes the arena any more).  *stream: where their kernels go.
 template <class Args> int batch_post_begin(xlz_batch *b, Args args, hipStream_t *stream)
@@ -2056,13 +2086,8 @@ extern "C" int xlz_batch_digests(xlz_batch *b, const xlz_check_range *ranges, si
     if (st != XLZ_OK) return st;
     xlz_check_stats acc = {};
     xlz_sha256_stats sha = {};
-    std::vector<uint64_t> crc(n);
-    st = batch_checks_run(b, ranges, nullptr, n, 0, crc.data(), stream, nullptr, acc);
-    if (st == XLZ_OK) st = batch_sha256_run(b, ranges, nullptr, n, 0, out, stream, nullptr, nullptr, sha);
+    st = batch_digests_run(b, PostWork{nullptr, 0, ranges, n, nullptr, out, false}, nullptr, n, 0, stream, nullptr, nullptr, acc, sha);
     if (st != XLZ_OK) return st;
-    for (size_t q = 0; q < n; q++)
-        if (ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &out[q]);
-    xlzpost::stats_add(acc, sha); // (the SHA-256 ranges count in xlz_check_stats too)
     publish(b->ctx, &xlz_ctx::last_check, acc, false);
     publish(b->ctx, &xlz_ctx::last_sha, sha, false);
     return XLZ_OK;
@@ -2085,15 +2110,8 @@ extern "C" int xlz_internal_batch_sha256_device(xlz_batch *b, const xlz_check_ra
 extern "C" double xlz_internal_sha256_host_bench(const uint8_t *p, size_t n, size_t reps, uint32_t threads)
 {
     std::vector<xlz_digest> out(reps);
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < reps;) xlzcheck::sha256(p, n, out[i].b);
-    };
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<std::thread> th;
-    for (uint32_t t = 1; t < threads; t++) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
+    xlzpost::parallel_for(reps, threads, [&](size_t i) { xlzcheck::sha256(p, n, out[i].b); });
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -2367,12 +2385,6 @@ int batch_pack_run(xlz_batch *b, const xlz_pack_item *items, size_t n, void *d_d
     return XLZ_OK;
 }
 
-void publish_pack(xlz_ctx *ctx, const xlz_pack_stats &v)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_pack = v;
-}
-
 } // namespace
 
 extern "C" int xlz_batch_pack(xlz_batch *b, const xlz_pack_item *items, size_t n, void *d_dst, size_t dst_cap, uint64_t *copied)
@@ -2389,7 +2401,7 @@ extern "C" int xlz_batch_pack(xlz_batch *b, const xlz_pack_item *items, size_t n
     if (st != XLZ_OK || !n) return st;
     xlz_pack_stats acc = {};
     st = batch_pack_run(b, items, n, d_dst, copied, stream, acc);
-    if (st == XLZ_OK) publish_pack(b->ctx, acc);
+    if (st == XLZ_OK) publish(b->ctx, &xlz_ctx::last_pack, acc, false);
     return st;
 }
 
@@ -2537,28 +2549,16 @@ int batch_bcj2_run(xlz_batch *b, const xlz_bcj2_item *items, size_t n, void *d_d
                 }
         }
         std::vector<int> status(on_host.size(), XLZ_OK);
-        std::atomic<size_t> next{0};
-        auto work = [&] {
-            for (size_t q; (q = next.fetch_add(1)) < on_host.size();) {
-                const size_t i = on_host[q];
-                const uint8_t *p[3];
-                for (int k = 0; k < 3; k++) p[k] = res[i].s[k].host ? res[i].s[k].host : down[3 * q + k].data();
-                merged[q].resize((size_t)items[i].out_len);
-                status[q] = host_merge(p[0], (size_t)res[i].s[0].len, p[1], (size_t)res[i].s[1].len, p[2], (size_t)res[i].s[2].len, items[i].rc,
-                                       (size_t)items[i].rc_len, merged[q].data(), merged[q].size(), nullptr) == kStOk
-                                ? XLZ_OK
-                                : XLZ_ERR_RESULT;
-            }
-        };
-        const unsigned hw = std::thread::hardware_concurrency();
-        const unsigned nth = (unsigned)std::min<size_t>(std::max(1u, std::min(hw ? hw : 1u, 16u)), on_host.size());
-        std::vector<std::thread> th;
-        try {
-            for (unsigned t = 1; t < nth; t++) th.emplace_back(work);
-        } catch (...) { // (no thread to be had: this one does it all)
-        }
-        work();
-        for (auto &x : th) x.join();
+        xlzpost::parallel_for(on_host.size(), xlzpost::host_thread_cap(16), [&](size_t q) {
+            const size_t i = on_host[q];
+            const uint8_t *p[3];
+            for (int k = 0; k < 3; k++) p[k] = res[i].s[k].host ? res[i].s[k].host : down[3 * q + k].data();
+            merged[q].resize((size_t)items[i].out_len);
+            status[q] = host_merge(p[0], (size_t)res[i].s[0].len, p[1], (size_t)res[i].s[1].len, p[2], (size_t)res[i].s[2].len, items[i].rc,
+                                   (size_t)items[i].rc_len, merged[q].data(), merged[q].size(), nullptr) == kStOk
+                            ? XLZ_OK
+                            : XLZ_ERR_RESULT;
+        });
         std::lock_guard<std::mutex> lock(ctx->mu);
         HIP_TRY(hipSetDevice(ctx->device));
         for (size_t q = 0; q < on_host.size(); q++) {
@@ -2570,67 +2570,6 @@ int batch_bcj2_run(xlz_batch *b, const xlz_bcj2_item *items, size_t n, void *d_d
             acc.host_items++, acc.host_bytes += items[i].out_len, acc.failed_items += !ok;
         }
     }
-    return XLZ_OK;
-}
-
-void publish_bcj2(xlz_ctx *ctx, const xlz_bcj2_stats &v, bool accumulate)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!accumulate) ctx->last_bcj2 = xlz_bcj2_stats{};
-    xlz_bcj2_stats &t = ctx->last_bcj2;
-    t.device_items += v.device_items, t.device_bytes += v.device_bytes, t.host_items += v.host_items, t.host_bytes += v.host_bytes;
-    t.failed_items += v.failed_items, t.kernel_ms += v.kernel_ms, t.launches += v.launches;
-}
-
-// The CRC32 of ranges of a caller-owned DEVICE buffer (the merged BCJ2 folders of xlz_7z_decode_device), by the check
-// kernels on `stream` with the batch's check scratch; waits.  The kernels read aligned lines: their base is d_dst rounded
-// down to 16, and nothing outside a range is read.
-int dest_checks_run(xlz_batch *b, const void *d_dst, const DestRange *ranges, size_t n, uint64_t *digests, hipStream_t stream, xlz_check_stats &acc)
-{
-    using xlzchk::DevRange;
-    const uint64_t mis = (uintptr_t)d_dst & 15;
-    std::vector<DevRange> dev;
-    std::vector<size_t> where;
-    uint64_t segs = 0, dev_bytes = 0;
-    for (size_t q = 0; q < n; q++) {
-        digests[q] = 0;
-        if (!ranges[q].len) {
-            acc.empty_ranges++;
-            continue;
-        }
-        DevRange d;
-        d.off = ranges[q].off + mis, d.len = ranges[q].len;
-        const uint64_t ns = xlzchk::range_segments(d.off, d.len);
-        if (segs + ns > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
-        d.seg_first = (uint32_t)segs, d.n_segs = (uint32_t)ns, d.out_index = (uint32_t)dev.size(), d.reserved = 0;
-        segs += ns, dev_bytes += d.len;
-        dev.push_back(d), where.push_back(q);
-    }
-    if (dev.empty()) return XLZ_OK;
-    xlz_ctx *ctx = b->ctx;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    HIP_TRY(hipSetDevice(ctx->device));
-    int st = check_tables(ctx);
-    if (st != XLZ_OK) return st;
-    const size_t tab_bytes = dev.size() * sizeof(DevRange), seg_bytes = (size_t)segs * 8, dig_bytes = dev.size() * 8;
-    st = b->chk.reserve(b, tab_bytes + seg_bytes + dig_bytes, tab_bytes + dig_bytes);
-    if (st != XLZ_OK) return st;
-    memcpy(b->chk.pin, dev.data(), tab_bytes);
-    uint64_t *h_dig = reinterpret_cast<uint64_t *>(b->chk.pin + tab_bytes);
-    DevRange *d_tab = reinterpret_cast<DevRange *>(b->chk.dev);
-    uint64_t *d_seg = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes), *d_dig = reinterpret_cast<uint64_t *>(b->chk.dev + tab_bytes + seg_bytes);
-    HIP_TRY(hipMemcpyAsync(d_tab, b->chk.pin, tab_bytes, hipMemcpyHostToDevice, stream));
-    float ms = 0;
-    st = timed_bracket(
-        stream, b->chk, "check kernels", &ms,
-        [&] {
-            return xlz::check_launch(32, static_cast<const uint8_t *>(d_dst) - mis, d_tab, (uint32_t)dev.size(), (uint32_t)segs, ctx->chk_tab[0],
-                                     ctx->chk_consts[0], d_seg, d_dig, ctx->num_cus, stream) == 0;
-        },
-        h_dig, d_dig, dig_bytes);
-    if (st != XLZ_OK) return st;
-    for (size_t j = 0; j < dev.size(); j++) digests[where[j]] = h_dig[j];
-    acc.device_ranges += dev.size(), acc.device_bytes += dev_bytes, acc.kernel_ms += ms, acc.launches++;
     return XLZ_OK;
 }
 
@@ -2659,7 +2598,7 @@ extern "C" int xlz_batch_bcj2(xlz_batch *b, const xlz_bcj2_item *items, size_t n
     if (st != XLZ_OK || !n) return st;
     xlz_bcj2_stats acc = {};
     st = batch_bcj2_run(b, items, n, d_dst, results, stream, xlz_ctx_bcj2_mode(b->ctx) == 2 ? 2 : 1, acc);
-    if (st == XLZ_OK) publish_bcj2(b->ctx, acc, false);
+    if (st == XLZ_OK) publish(b->ctx, &xlz_ctx::last_bcj2, acc, false);
     return st;
 }
 
@@ -2673,7 +2612,7 @@ extern "C" int xlz_ctx_set_bcj2_mode(xlz_ctx *ctx, int mode)
 extern "C" int xlz_ctx_bcj2_mode(const xlz_ctx *ctx) { return ctx ? ctx->bcj2_mode : XLZ_ERR_BAD_ARG; }
 extern "C" int xlz_ctx_last_bcj2_stats(xlz_ctx *ctx, xlz_bcj2_stats *out) { return last_stats(ctx, &xlz_ctx::last_bcj2, out); }
 
-void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx) { publish_bcj2(ctx, xlz_bcj2_stats{}, false); }
+void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_bcj2, xlz_bcj2_stats{}, false); }
 
 int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p)
 {
@@ -3078,10 +3017,10 @@ extern "C" int xlz_decode_batch_plan(const xlz_stream_desc *streams, size_t n, s
 namespace {
 
 // XLZ_ERR_BAD_ARG for work that the library does not run behind these n streams
-int post_args(const PostWork &w, const xlz_stream_desc *streams, size_t n)
+int post_args(const PostWork &w, const xlz_stream_desc *streams, size_t n, bool dest_too = false)
 {
     const void *out = w.digest_out ? (const void *)w.digest_out : (const void *)w.crc_out;
-    if (check_args(w.ranges, w.n_ranges, n, out, w.digest_out != nullptr) != XLZ_OK || filter_args(w.steps, w.n_steps, n) != XLZ_OK)
+    if (check_args(w.ranges, w.n_ranges, n, out, w.digest_out != nullptr, dest_too) != XLZ_OK || filter_args(w.steps, w.n_steps, n) != XLZ_OK)
         return XLZ_ERR_BAD_ARG;
     for (size_t q = 0; q < w.n_steps; q++)
         if (streams[w.steps[q].stream].flags & XLZ_STREAM_F_LZMA2_SLICE) return XLZ_ERR_BAD_ARG; // (a filter needs the stream's start)
@@ -3101,10 +3040,7 @@ struct PostStage {
     const xlz_stream_desc *streams;
     const std::vector<size_t> &cuts;
     std::vector<std::vector<size_t>> sub_steps, sub_ranges; // of every sub-batch, in array order
-    // digest_out: the CRCs go through a table of this call and are put into digest_out[] at the end; the SHA-256 ranges
-    // run behind the CRC ranges of their sub-batch, those the host hashes when the call's bytes are in place
-    std::vector<uint64_t> crc_of;
-    uint64_t *crc;
+    // the SHA-256 ranges that the host hashes when the call's bytes are in place
     std::vector<ShaHostJob> sha_later;
     xlz_filter_stats flt = {};
     xlz_check_stats chk = {};
@@ -3112,7 +3048,7 @@ struct PostStage {
 
     PostStage(const PostWork &w_, xlz_ctx *ctx_, const xlz_stream_desc *streams_, const std::vector<size_t> &cuts_)
         : w(w_), ctx(ctx_), streams(streams_), cuts(cuts_), sub_steps(w_.n_steps ? cuts_.size() - 1 : 0),
-          sub_ranges(w_.n_ranges ? cuts_.size() - 1 : 0), crc_of(w_.digest_out ? w_.n_ranges : 0), crc(w_.digest_out ? crc_of.data() : w_.crc_out)
+          sub_ranges(w_.n_ranges ? cuts_.size() - 1 : 0)
     {
         auto sub_of = [&](uint64_t stream) { return (size_t)(std::upper_bound(cuts.begin(), cuts.end(), (size_t)stream) - cuts.begin()) - 1; };
         for (size_t q = 0; q < w.n_steps; q++) sub_steps[sub_of(w.steps[q].stream)].push_back(q);
@@ -3141,11 +3077,7 @@ struct PostStage {
     }
     int after_publish(size_t k, xlz_batch *b) // for a k that has_ranges
     {
-        const std::vector<size_t> &idx = sub_ranges[k];
-        int e = batch_checks_run(b, w.ranges, idx.data(), idx.size(), cuts[k], crc, ctx->check_stream, streams + cuts[k], chk);
-        if (e == XLZ_OK && w.digest_out) // (it looks for the XLZ_CHECK_SHA256 ranges among them)
-            e = batch_sha256_run(b, w.ranges, idx.data(), idx.size(), cuts[k], w.digest_out, ctx->check_stream, streams + cuts[k], &sha_later, sha);
-        return e;
+        return batch_digests_run(b, w, sub_ranges[k].data(), sub_ranges[k].size(), cuts[k], ctx->check_stream, streams + cuts[k], &sha_later, chk, sha);
     }
     // `big`: the streams of 4 GiB and more (sorted), which no batch held: their sessions have written the callers' buffers.
     // They are settled there, the filters first and in array order, then the checks; the statistics become the context's.
@@ -3171,6 +3103,7 @@ struct PostStage {
             publish(ctx, &xlz_ctx::last_filter, flt, w.accumulate);
         }
         if (!w.n_ranges) return;
+        xlz_sha256_stats big_sha = {};
         for (size_t q = 0; q < w.n_ranges && !big.empty(); q++) {
             const xlz_check_range &r = w.ranges[q];
             if (!is_big(r.stream)) continue;
@@ -3179,21 +3112,23 @@ struct PostStage {
             const uint64_t len = c.hi - c.lo;
             if (r.kind == XLZ_CHECK_SHA256) {
                 if (len)
-                    sha_later.push_back(ShaHostJob{p, len, &w.digest_out[q]}), sha.host_ranges++, sha.host_bytes += len;
+                    sha_later.push_back(ShaHostJob{p, len, &w.digest_out[q]}), big_sha.host_ranges++, big_sha.host_bytes += len;
                 else
-                    sha256_of_nothing(&w.digest_out[q]), sha.empty_ranges++;
+                    sha256_of_nothing(&w.digest_out[q]), big_sha.empty_ranges++;
                 continue;
             }
-            crc[q] = len ? host_digest(r.kind, p, len) : 0;
+            const uint64_t v = len ? host_digest(r.kind, p, len) : 0;
+            if (w.digest_out)
+                crc_digest(v, &w.digest_out[q]);
+            else
+                w.crc_out[q] = v;
             if (len)
                 chk.host_ranges++, chk.host_bytes += len;
             else
                 chk.empty_ranges++;
         }
         sha256_host_jobs(sha_later);
-        for (size_t q = 0; q < w.n_ranges && w.digest_out; q++)
-            if (w.ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &w.digest_out[q]);
-        xlzpost::stats_add(chk, sha); // (the SHA-256 ranges count in xlz_check_stats too)
+        xlzpost::stats_add(chk, big_sha), xlzpost::stats_add(sha, big_sha); // (the SHA-256 ranges count in xlz_check_stats too)
         if (w.digest_out) publish(ctx, &xlz_ctx::last_sha, sha, w.accumulate, xlzpost::ThresholdIsMax{});
         publish(ctx, &xlz_ctx::last_check, chk, w.accumulate);
     }
@@ -3496,12 +3431,25 @@ int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size
     return decode_batch_impl(ctx, streams, n, results, post);
 }
 
-// xlz_check_host.h: the device-destination form, what xlz_xz_decode_device and xlz_7z_decode_device are built on
+// xlz_check_host.h: the device-destination form, what xlz_xz_decode_device and xlz_7z_decode_device are built on.  One
+// batch on the context's stream, and behind it a line of stages that each publish what they did: the filters, the
+// digests of the ranges over streams, the pack, the BCJ2 merges, the digests of the ranges over the destination, the copies.
 int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
                                const DeviceDest &dest)
 {
     if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || !dest.dst_off))) return XLZ_ERR_BAD_ARG;
-    if (post_args(post, streams, n) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    if (post_args(post, streams, n, true) != XLZ_OK) return XLZ_ERR_BAD_ARG;
+    std::vector<size_t> of_streams, of_dest; // post.ranges by where their bytes lie
+    for (size_t q = 0; q < post.n_ranges; q++) {
+        const xlz_check_range &r = post.ranges[q];
+        uint64_t at;
+        if (r.stream != xlzpost::kDestStream)
+            of_streams.push_back(q);
+        else if (r.kind == XLZ_CHECK_SHA256 || !n || !xlzpost::dest_resolve(r.off, r.len, dest.cap, 0, &at))
+            return XLZ_ERR_BAD_ARG;
+        else
+            of_dest.push_back(q);
+    }
     std::vector<xlz_pack_item> items;
     for (size_t i = 0; i < n; i++)
         if (!(dest.no_pack && dest.no_pack[i])) items.push_back(xlz_pack_item{i, 0, dest.want_out[i], dest.dst_off[i]});
@@ -3509,14 +3457,21 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         if (dest.copies[k].dst_off > dest.cap || dest.copies[k].len > dest.cap - dest.copies[k].dst_off) return XLZ_ERR_BAD_ARG;
     if (!xlzpost::pack_items_ok(items.data(), items.size(), n, dest.cap)) return XLZ_ERR_BAD_ARG;
     if (dest.n_bcj2 && (!n || !dest.bcj2 || !dest.bcj2_res || !bcj2_items_ok(dest.bcj2, dest.n_bcj2, n, dest.cap))) return XLZ_ERR_BAD_ARG;
-    for (size_t q = 0; q < dest.n_dranges; q++)
-        if (!dest.ddigests || dest.dranges[q].off > dest.cap || dest.dranges[q].len > dest.cap - dest.dranges[q].off) return XLZ_ERR_BAD_ARG;
     if (dest.cap) {
         const int ok = device_dst_ok(ctx, dest.d_dst, dest.cap);
         if (ok != XLZ_OK) return ok;
     }
     xlz_batch *b = nullptr;
     int st = XLZ_OK;
+    hipStream_t stream = ctx->stream; // (a batch of xlz_batch_create runs there)
+    auto digests = [&](const std::vector<size_t> &idx, const DeviceDest *dst) {
+        xlz_check_stats chk = {};
+        xlz_sha256_stats sha = {};
+        st = batch_digests_run(b, post, idx.data(), idx.size(), 0, stream, nullptr, nullptr, chk, sha, dst);
+        if (st != XLZ_OK || idx.empty()) return;
+        if (post.digest_out) publish(ctx, &xlz_ctx::last_sha, sha, true, xlzpost::ThresholdIsMax{});
+        publish(ctx, &xlz_ctx::last_check, chk, true);
+    };
     if (n) {
         st = xlz_batch_create(ctx, streams, n, &b);
         for (size_t i = 0; i < n && st == XLZ_OK; i++)
@@ -3528,44 +3483,23 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
                 st = results[i].status;
             else if (results[i].out_len != dest.want_out[i] || (dest.want_in && results[i].in_consumed != dest.want_in[i]))
                 st = XLZ_ERR_RESULT;
-        hipStream_t stream = ctx->stream; // (a batch of xlz_batch_create runs there)
         if (st == XLZ_OK && post.n_steps) {
             xlz_filter_stats flt = {};
             st = batch_filter_run(b, post.steps, nullptr, post.n_steps, 0, stream, flt);
             if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_filter, flt, true);
         }
-        if (st == XLZ_OK && post.n_ranges) {
-            xlz_check_stats chk = {};
-            xlz_sha256_stats sha = {};
-            std::vector<uint64_t> crc_of(post.digest_out ? post.n_ranges : 0);
-            uint64_t *crc = post.digest_out ? crc_of.data() : post.crc_out;
-            st = batch_checks_run(b, post.ranges, nullptr, post.n_ranges, 0, crc, stream, nullptr, chk);
-            if (st == XLZ_OK && post.digest_out) {
-                st = batch_sha256_run(b, post.ranges, nullptr, post.n_ranges, 0, post.digest_out, stream, nullptr, nullptr, sha);
-                for (size_t q = 0; q < post.n_ranges && st == XLZ_OK; q++)
-                    if (post.ranges[q].kind != XLZ_CHECK_SHA256) crc_digest(crc[q], &post.digest_out[q]);
-            }
-            if (st == XLZ_OK) {
-                xlzpost::stats_add(chk, sha); // (the SHA-256 ranges count in xlz_check_stats too)
-                if (post.digest_out) publish(ctx, &xlz_ctx::last_sha, sha, true, xlzpost::ThresholdIsMax{});
-                publish(ctx, &xlz_ctx::last_check, chk, true);
-            }
-        }
+        if (st == XLZ_OK) digests(of_streams, nullptr);
         if (st == XLZ_OK) {
             xlz_pack_stats pk = {};
             st = batch_pack_run(b, items.data(), items.size(), dest.d_dst, nullptr, stream, pk);
-            if (st == XLZ_OK) publish_pack(ctx, pk);
+            if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_pack, pk, false);
         }
         if (st == XLZ_OK && dest.n_bcj2) { // the BCJ2 folders: merged into the destination, then checked THERE
             xlz_bcj2_stats bj = {};
             st = batch_bcj2_run(b, dest.bcj2, dest.n_bcj2, dest.d_dst, dest.bcj2_res, stream, dest.bcj2_mode == 2 ? 2 : 1, bj);
-            if (st == XLZ_OK) publish_bcj2(ctx, bj, true);
-            if (st == XLZ_OK && dest.n_dranges) {
-                xlz_check_stats chk = {};
-                st = dest_checks_run(b, dest.d_dst, dest.dranges, dest.n_dranges, dest.ddigests, stream, chk);
-                if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_check, chk, true);
-            }
+            if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_bcj2, bj, true);
         }
+        if (st == XLZ_OK) digests(of_dest, &dest);
     }
     if (hipSetDevice(ctx->device) != hipSuccess) st = st == XLZ_OK ? XLZ_ERR_DEVICE : st;
     for (size_t k = 0; k < dest.n_copies && st == XLZ_OK; k++)

@@ -1,10 +1,13 @@
 // xlz_post.h -- what the post-decode stage of xlz_host.hip (filters, CRC32 / CRC64, SHA-256 behind a collected batch)
-// decides without a device: which bytes of a stream a range means and where they lie, and how its statistics add up.
+// decides without a device: which bytes of a stream or of a device destination a range means and where they lie, how its
+// statistics add up, and how its host work is spread over threads.
 // Plain C++ (tests/c/post_selftest.cpp runs it without a GPU); not part of the C ABI.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -53,6 +56,19 @@ inline Clip clip(const StreamOut &s, uint64_t off, uint64_t len)
 }
 constexpr uint64_t kWholeStream = ~(uint64_t)0; // clip(s, 0, kWholeStream): all the stream produced (a filter step)
 
+// xlz_check_range::stream of a range that names no stream but bytes [off, off + len) of the DESTINATION of
+// xlz_internal_decode_device (xlz_check_host.h).  Internal: no batch has that many streams, so the public calls refuse it.
+constexpr uint64_t kDestStream = ~(uint64_t)0;
+// Such a range for the check kernels, which read aligned lines: their base is the destination pointer rounded down to 16,
+// `mis` (pointer & 15) bytes in front of it.  -> *at: the range's offset behind that base; false: [off, off + len) does
+// not lie inside the destination's `cap` bytes (no sum is formed unless it fits).  An empty range may sit at `cap`.
+inline bool dest_resolve(uint64_t off, uint64_t len, uint64_t cap, uint64_t mis, uint64_t *at)
+{
+    if (mis > 15 || cap > ~(uint64_t)0 - mis || off > cap || len > cap - off) return false;
+    *at = off + mis;
+    return true;
+}
+
 // xlz_check_stats, xlz_sha256_stats and xlz_filter_stats share seven counters; the filters call their ranges steps
 template <class T> struct Counts {
     static constexpr uint64_t T::*device = &T::device_ranges, T::*host = &T::host_ranges, T::*empty = &T::empty_ranges;
@@ -73,6 +89,41 @@ inline void stats_add(xlz_sha256_stats &t, const xlz_sha256_stats &a, ThresholdI
 {
     stats_add(t, a);
     t.threshold = std::max(t.threshold, a.threshold);
+}
+
+// t += a for the pack's and the BCJ2 merge's counters (no two of these share a layout with the seven above)
+inline void stats_add(xlz_pack_stats &t, const xlz_pack_stats &a)
+{
+    t.items += a.items, t.bytes += a.bytes, t.empty_items += a.empty_items, t.congruent_items += a.congruent_items;
+    t.kernel_ms += a.kernel_ms, t.launches += a.launches;
+}
+inline void stats_add(xlz_bcj2_stats &t, const xlz_bcj2_stats &a)
+{
+    t.device_items += a.device_items, t.device_bytes += a.device_bytes, t.host_items += a.host_items, t.host_bytes += a.host_bytes;
+    t.failed_items += a.failed_items, t.kernel_ms += a.kernel_ms, t.launches += a.launches;
+}
+
+// min(cap, the machine's hardware threads), at least 1: how many host threads a stage may use
+inline unsigned host_thread_cap(unsigned cap)
+{
+    const unsigned hw = std::thread::hardware_concurrency();
+    return std::max(1u, std::min(hw ? hw : 1u, cap));
+}
+// f(i) for every i in [0, n), each once, on at most k threads of which the caller is one: every thread takes the next i
+// that nobody has.  Where a thread cannot be created, those that exist (the caller at least) do the rest.  f must not throw.
+template <class F> void parallel_for(size_t n, size_t k, F &&f)
+{
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
+    };
+    std::vector<std::thread> th;
+    try {
+        for (size_t t = 1; t < k && t < n; t++) th.emplace_back(work);
+    } catch (...) {
+    }
+    work();
+    for (auto &x : th) x.join();
 }
 
 // xlz_batch_pack's table as the caller declares it: every item names a stream of the batch, its destination range

@@ -16,7 +16,6 @@
 #include <cstdint>
 #include <cstring>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/xlz.h"
@@ -30,6 +29,7 @@ using xlzcheck::crc32;
 using xlzcheck::crc64;
 
 uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | (uint64_t)le32(p + 4) << 32; }
 
 // variable-length integer (spec 1.2): 7 bits per byte, at most 9 bytes, no trailing zero byte
 bool vli(const uint8_t *p, size_t n, size_t &pos, uint64_t &v)
@@ -372,32 +372,24 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     }
     if (verify) {
         std::vector<int> bad(nb, 0);
-        const unsigned hw = std::thread::hardware_concurrency();
-        const unsigned nth = (unsigned)std::min<size_t>(std::max<size_t>(1, std::min<unsigned>(hw ? hw : 1, 16)), std::max<size_t>(nb, 1));
-        auto work = [&](unsigned t) {
-            for (size_t i = t; i < nb; i += nth) {
-                const uint8_t *p = out ? out + blk[i].uncomp_off : nullptr; // (a device destination: every check below is the device's)
-                const uint8_t *c = file + blk[i].check_off;
-                if (dev && (blk[i].check_type == 1 || blk[i].check_type == 4))
-                    bad[i] = dg[i] != (blk[i].check_type == 1 ? (uint64_t)le32(c) : ((uint64_t)le32(c) | (uint64_t)le32(c + 4) << 32));
-                else if (blk[i].check_type == 1)
-                    bad[i] = crc32(p, (size_t)blk[i].uncomp_len) != le32(c);
-                else if (blk[i].check_type == 4)
-                    bad[i] = crc64(p, (size_t)blk[i].uncomp_len) != ((uint64_t)le32(c) | (uint64_t)le32(c + 4) << 32);
-                else if (blk[i].check_type == 10 && dev_sha)
-                    bad[i] = memcmp(xdg[i].b, c, 32) != 0;
-                else if (blk[i].check_type == 10) {
-                    uint8_t dg[32];
-                    xlzcheck::sha256(p, (size_t)blk[i].uncomp_len, dg);
-                    bad[i] = memcmp(dg, c, 32) != 0;
-                } else if (blk[i].check_type != 0)
-                    bad[i] = 2; // reserved check types: not verified
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nth; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
+        xlzpost::parallel_for(nb, xlzpost::host_thread_cap(16), [&](size_t i) {
+            const uint8_t *p = out ? out + blk[i].uncomp_off : nullptr; // (a device destination: every check below is the device's)
+            const uint8_t *c = file + blk[i].check_off;
+            if (dev && (blk[i].check_type == 1 || blk[i].check_type == 4))
+                bad[i] = dg[i] != (blk[i].check_type == 1 ? (uint64_t)le32(c) : le64(c));
+            else if (blk[i].check_type == 1)
+                bad[i] = crc32(p, (size_t)blk[i].uncomp_len) != le32(c);
+            else if (blk[i].check_type == 4)
+                bad[i] = crc64(p, (size_t)blk[i].uncomp_len) != le64(c);
+            else if (blk[i].check_type == 10 && dev_sha)
+                bad[i] = memcmp(xdg[i].b, c, 32) != 0;
+            else if (blk[i].check_type == 10) {
+                uint8_t dg[32];
+                xlzcheck::sha256(p, (size_t)blk[i].uncomp_len, dg);
+                bad[i] = memcmp(dg, c, 32) != 0;
+            } else if (blk[i].check_type != 0)
+                bad[i] = 2; // reserved check types: not verified
+        });
         if (dev && !dev_sha)
             for (size_t i = 0; i < nb; i++)
                 if (blk[i].check_type == 10) xlz_internal_check_stats_host(ctxs[0], 1, blk[i].uncomp_len);

@@ -1,8 +1,11 @@
 // What the post-decode stage decides without a device (lzma_amd/csrc/xlz_post.h): which bytes of a stream a range means
 // and where they lie -- among them the streams of 4 GiB and more, which no GPU test of a few seconds reaches --, and how
-// the three statistics add up.  Prints "ok" and exits 0, or says what differs.
+// the statistics add up; where a range of a device destination lies for the check kernels; and the host-thread helper.
+// Prints "ok" and exits 0, or says what differs.  "threads" as the only argument: the thread helper alone (the part to
+// run under -fsanitize=thread).
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 
 #include "xlz_post.h"
 
@@ -99,10 +102,84 @@ static void stats()
     EQ(f2.kernel_ms, 4.0), EQ(f2.launches, 14u);
 }
 
-int main()
+static void more_stats()
 {
-    clips();
-    stats();
+    xlz_pack_stats p, p2;
+    xlz_bcj2_stats b, b2;
+    memset(&p, 0, sizeof p), memset(&b, 0, sizeof b);
+    p.items = 1, p.bytes = 2, p.congruent_items = 3, p.empty_items = 4, p.kernel_ms = 0.5, p.launches = 5, p.reserved = 9;
+    p2 = p;
+    stats_add(p2, p);
+    EQ(p2.items, 2u), EQ(p2.bytes, 4u), EQ(p2.congruent_items, 6u), EQ(p2.empty_items, 8u), EQ(p2.kernel_ms, 1.0), EQ(p2.launches, 10u);
+    EQ(p2.reserved, 9u);
+    b.device_items = 1, b.device_bytes = 2, b.host_items = 3, b.host_bytes = 4, b.failed_items = 5, b.kernel_ms = 0.25, b.launches = 6;
+    b.reserved = 9;
+    b2 = b;
+    stats_add(b2, b);
+    stats_add(b2, xlz_bcj2_stats{}); // (a reset front-end that merged nothing)
+    EQ(b2.device_items, 2u), EQ(b2.device_bytes, 4u), EQ(b2.host_items, 6u), EQ(b2.host_bytes, 8u), EQ(b2.failed_items, 10u);
+    EQ(b2.kernel_ms, 0.5), EQ(b2.launches, 12u), EQ(b2.reserved, 9u);
+}
+
+static void dest_ranges()
+{
+    const uint64_t cap = 1000;
+    for (uint64_t mis = 0; mis < 16; mis++) { // all 16 misalignments: the range moves behind the rounded-down base by just that
+        uint64_t at = 77;
+        EQ(dest_resolve(0, 10, cap, mis, &at), true), EQ(at, mis);
+        EQ(dest_resolve(cap - 10, 10, cap, mis, &at), true), EQ(at, cap - 10 + mis); // off == cap - len: the last bytes
+        EQ(dest_resolve(cap, 0, cap, mis, &at), true), EQ(at, cap + mis);            // off == cap holds an empty range only
+        EQ(dest_resolve(cap, 1, cap, mis, &at), false);
+        EQ(dest_resolve(cap - 10, 11, cap, mis, &at), false);
+        EQ(dest_resolve(0, 0, cap, mis, &at), true), EQ(at, mis); // len 0
+        EQ(dest_resolve(0, cap, cap, mis, &at), true);
+        EQ(dest_resolve(0, cap + 1, cap, mis, &at), false);
+        EQ(dest_resolve(cap + 1, 0, cap, mis, &at), false);
+        // sums that would wrap: off + len, and a destination so large that cap + mis does
+        EQ(dest_resolve(1, kMax, cap, mis, &at), false), EQ(dest_resolve(kMax, 1, cap, mis, &at), false);
+        EQ(dest_resolve(kMax, kMax, cap, mis, &at), false), EQ(dest_resolve(500, kMax - 499, cap, mis, &at), false);
+        EQ(dest_resolve(kMax - 20, 5, kMax, mis, &at), mis == 0);
+        EQ(dest_resolve(0, 0, kMax - mis, mis, &at), true), EQ(dest_resolve(kMax - 15, 0, kMax - 15, mis, &at), mis <= 15);
+    }
+    uint64_t at = 77;
+    EQ(dest_resolve(0, 1, cap, 16, &at), false), EQ(at, 77u); // a misalignment is pointer & 15
+    EQ(dest_resolve(0, 0, 0, 0, &at), true), EQ(at, 0u);      // an empty destination holds an empty range
+    EQ(dest_resolve(0, 1, 0, 0, &at), false);
+    EQ(kDestStream, kMax); // no batch has that many streams: the public calls refuse the index
+}
+
+// n indices on at most k threads: every index exactly once, whatever n and k; host_thread_cap stays inside [1, cap]
+static void threads()
+{
+    const struct {
+        size_t n, k;
+    } shapes[] = {{0, 4}, {1, 4}, {1, 0}, {3, 8}, {5, 1}, {5, 0}, {16, 16}, {100000, 7}, {4096, 16}};
+    for (const auto &sh : shapes) {
+        std::vector<uint32_t> hit(sh.n, 0); // (each index is its own element: no two threads share one)
+        std::atomic<size_t> calls{0};
+        parallel_for(sh.n, sh.k, [&](size_t i) { hit[i]++, calls.fetch_add(1); });
+        size_t once = 0;
+        for (uint32_t h : hit) once += h == 1;
+        EQ(once, sh.n), EQ(calls.load(), sh.n);
+    }
+    std::vector<uint64_t> sq(1000);
+    parallel_for(sq.size(), host_thread_cap(16), [&](size_t i) { sq[i] = (uint64_t)i * i; });
+    EQ(std::accumulate(sq.begin(), sq.end(), (uint64_t)0), (uint64_t)332833500);
+    for (unsigned cap : {0u, 1u, 8u, 16u, 1000u}) {
+        const unsigned t = host_thread_cap(cap);
+        EQ(t >= 1 && (t <= cap || t == 1), true);
+    }
+}
+
+int main(int argc, char **argv)
+{
+    if (argc <= 1 || strcmp(argv[1], "threads") != 0) {
+        clips();
+        stats();
+        more_stats();
+        dest_ranges();
+    }
+    threads();
     if (failures) return printf("%d failures\n", failures), 1;
     printf("ok\n");
     return 0;
