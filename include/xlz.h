@@ -659,6 +659,61 @@ int xlz_xz_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_
 int xlz_xz_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out,
                         size_t out_cap, uint64_t *out_len, int verify, size_t *unverified);
 
+/* ---- byte ranges of an .xz file ---------------------------------------
+ * The index at the end of an .xz file says where every block's bytes lie in the decoded file, so bytes [off, off + len)
+ * of the DECODED file cost the blocks that hold them and nothing else.  xlz_xz_open parses the file once -- as
+ * xlz_xz_index_chains does, with the same status for every input -- and keeps the block table, the filter steps and a
+ * BORROWED pointer to `file`: the caller keeps those bytes alive and unchanged until xlz_xz_close (an mmap is fine; a
+ * read touches only the payloads and check fields of the blocks it decodes).  The handle never changes afterwards: any
+ * number of threads and contexts may use one at once.  Open, close, info, blocks and cover are host only, no device
+ * needed.  xlz_xz_file_blocks: the table as xlz_xz_index_chains gives it (XLZ_ERR_OUT_CAP: more blocks than max_blocks).
+ *
+ * A range is clipped to the decoded size like pread: copied[i] (copied may be NULL) = the bytes written for range i, 0
+ * for len == 0 or off >= size.  Two ranges may read the same bytes.  xlz_xz_cover: the ascending, duplicate-free
+ * indices of the blocks the ranges touch, by binary search over uncomp_off (blocks may be NULL with max_blocks 0 to
+ * obtain the count; XLZ_ERR_OUT_CAP: more than max_blocks).
+ *
+ * xlz_xz_read_device: ONE batch of the covering blocks -- each decoded once, however many ranges hit it --, then on the
+ * device the filter steps of those blocks (filter mode 1; a covering block with a filter chain on a context in filter
+ * mode 0 is XLZ_ERR_UNSUPPORTED, a chain on a block outside the cover never matters), the checks and ONE pack of
+ * (range, block) pieces to d_out + dst_off.  verify != 0 verifies every covering block's check over the WHOLE block,
+ * through the check kernels and the xlz_batch_digests path as xlz_xz_decode_device does; *unverified (optional) = the
+ * covering blocks whose check type is a reserved one.  A covering block must produce what the index says and use its
+ * whole payload (XLZ_ERR_RESULT, or the block's own status), and one of 4 GiB or more is XLZ_ERR_UNSUPPORTED.  Damage
+ * in a block outside the cover is not seen.  xlz_xz_read: the same into host memory, through a device staging buffer of
+ * the sum of the clipped lengths that the context keeps for the next read (xlz_ctx_trim releases it).
+ * XLZ_ERR_BAD_ARG: NULL arguments with n > 0; a clipped destination [dst_off, dst_off + copied[i]) that does not fit
+ * out_cap; two clipped destinations that share a byte (these are tested before the context is used; a range clipped to
+ * nothing declares no byte, wherever its dst_off points); d_out that is not out_cap bytes of device memory of the
+ * context's device.  Such a call, and one refused for a covering chain in filter mode 0, launches nothing, writes
+ * nothing and leaves every statistic as it was.  On every failure all copied[i] are 0 and the contents of the
+ * destination ranges are unspecified; bytes that no range covers are never written.  The call holds the arena of the
+ * covering blocks plus the destination (or staging), and returns when its device work is done.                    */
+typedef struct xlz_xz_file xlz_xz_file;
+int xlz_xz_open(const uint8_t *file, size_t len, xlz_xz_file **f);
+void xlz_xz_close(xlz_xz_file *f);
+int xlz_xz_file_info(const xlz_xz_file *f, uint64_t *size, size_t *n_blocks, size_t *n_steps);
+int xlz_xz_file_blocks(const xlz_xz_file *f, xlz_xz_block *blocks, size_t max_blocks);
+typedef struct xlz_xz_range {
+    uint64_t off, len; /* bytes of the DECODED file, clipped to its size                                 */
+    uint64_t dst_off;  /* where they go in the destination                                               */
+} xlz_xz_range;
+int xlz_xz_cover(const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, size_t *blocks, size_t max_blocks,
+                 size_t *n_blocks);
+int xlz_xz_read(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, uint8_t *out, size_t out_cap,
+                uint64_t *copied, int verify, size_t *unverified);
+int xlz_xz_read_device(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, void *d_out,
+                       size_t out_cap, uint64_t *copied, int verify, size_t *unverified);
+/* Of the most recent xlz_xz_read / xlz_xz_read_device on `ctx` (which also starts the check, SHA-256, filter and pack
+ * statistics over and fills them).                                                                                  */
+typedef struct xlz_xz_read_stats {
+    uint64_t ranges, empty_ranges; /* as given; of them clipped to nothing                                */
+    uint64_t blocks, comp_bytes;   /* the cover: the blocks decoded and their payload bytes               */
+    uint64_t decoded_bytes;        /* the sum of the covering blocks' decoded sizes                       */
+    uint64_t copied_bytes;         /* the sum of copied[] (0 when the read failed)                        */
+} xlz_xz_read_stats;
+int xlz_ctx_last_xz_read_stats(xlz_ctx *ctx, xlz_xz_read_stats *out);
+
 /* ---- .7z container front-end ----------------------------
  * (The parser was written from 7-Zip's published format description.  It is exercised on archives
  * built from that description by tests/sevenzip_craft.py and their mutations AND on archives by an

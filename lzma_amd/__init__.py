@@ -63,6 +63,7 @@ class Context:
 
     def __init__(self, device=0):
         self._h = ctypes.c_void_p()
+        self.last_xz_unverified = 0
         st = N.lib().xlz_ctx_create(device, ctypes.byref(self._h))
         if st != OK:
             raise LzmaError(st, "xlz_ctx_create(device=%d)" % device)
@@ -162,6 +163,16 @@ class Context:
         if st != OK:
             raise LzmaError(st, "xlz_ctx_last_pack_stats")
         return {k: getattr(ps, k) for k, _ in N.PackStats._fields_ if k != "reserved"}
+
+    def last_xz_read_stats(self):
+        """what the last XzFile.read / read_ranges / read_device / read_tensor on this context decoded and copied
+        (xlz_ctx_last_xz_read_stats) -> dict: blocks, comp_bytes and decoded_bytes are those of the covering blocks.  Such a
+        read also leaves its *unverified -- covering blocks with a reserved check type -- in self.last_xz_unverified."""
+        rs = N.XzReadStats()
+        st = N.lib().xlz_ctx_last_xz_read_stats(self._h, ctypes.byref(rs))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_xz_read_stats")
+        return {k: getattr(rs, k) for k, _ in N.XzReadStats._fields_}
 
     def set_bcj2_mode(self, mode):
         """what sevenzip_decode / sevenzip_decode_device do with BCJ2 folders (xlz_ctx_set_bcj2_mode): 0 refuse them (default),
@@ -1081,3 +1092,124 @@ def sevenzip_decode_tensor(ctx, data, verify=True, out=None):
     """sevenzip_decode_device into a torch.uint8 tensor on the context's device, as xz_decode_tensor"""
     total = _sevenzip_total(ctx, data)
     return _decode_tensor(sevenzip_decode_device, total, ctx, data, verify, out)
+
+
+# ---- byte ranges of an .xz file (include/xlz.h: xlz_xz_open / xlz_xz_cover / xlz_xz_read / xlz_xz_read_device) ----
+class _PyBuffer(ctypes.Structure):  # Py_buffer of the C API: what PyObject_GetBuffer fills in
+    _fields_ = [("buf", ctypes.c_void_p), ("obj", ctypes.py_object), ("len", ctypes.c_ssize_t), ("itemsize", ctypes.c_ssize_t),
+                ("readonly", ctypes.c_int), ("ndim", ctypes.c_int), ("format", ctypes.c_char_p), ("shape", ctypes.POINTER(ctypes.c_ssize_t)),
+                ("strides", ctypes.POINTER(ctypes.c_ssize_t)), ("suboffsets", ctypes.POINTER(ctypes.c_ssize_t)), ("internal", ctypes.c_void_p)]
+
+
+class XzFile:
+    """The parsed index of one .xz file (xlz_xz_open; host only): reads of byte ranges of the DECODED file decode the blocks
+    that hold them and nothing else.  `data` is bytes or any contiguous buffer (bytearray, memoryview, mmap -- read-only
+    ones too): it is borrowed through the buffer protocol, never copied, and held until close().  Raises LzmaError as
+    xz_index_chains does.  Read-only once made: one XzFile may serve several threads and contexts.  A context manager;
+    close() may be repeated."""
+
+    def __init__(self, data):
+        self._h = ctypes.c_void_p()
+        self._view = _PyBuffer()
+        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:  # (raises: no buffer, not contiguous)
+            raise TypeError("XzFile needs bytes or a contiguous buffer")
+        self._held = True
+        try:
+            st = N.lib().xlz_xz_open(ctypes.c_void_p(self._view.buf), self._view.len, ctypes.byref(self._h))
+            if st != OK:
+                self._h = ctypes.c_void_p()
+                raise LzmaError(st, "xlz_xz_open")
+            size, nb, ns = ctypes.c_uint64(), ctypes.c_size_t(), ctypes.c_size_t()
+            N.lib().xlz_xz_file_info(self._h, ctypes.byref(size), ctypes.byref(nb), ctypes.byref(ns))
+            self.size = size.value
+            blocks = (N.XzBlock * max(nb.value, 1))()
+            st = N.lib().xlz_xz_file_blocks(self._h, blocks, nb.value)
+            if st != OK:
+                raise LzmaError(st, "xlz_xz_file_blocks")
+        except Exception:
+            self.close()
+            raise
+        fields = [f for f, _ in N.XzBlock._fields_]
+        self.blocks = [{f: getattr(blocks[i], f) for f in fields} for i in range(nb.value)]
+        self.steps = ns.value  # how many filter steps the blocks carry (xz_index_chains lists them)
+
+    def _handle(self):
+        if not self._h:
+            raise LzmaError(ERR_CLOSED, "XzFile is closed")
+        return self._h
+
+    @staticmethod
+    def _ranges(ranges):
+        arr = (N.XzRange * max(len(ranges), 1))()
+        for i, r in enumerate(ranges):
+            arr[i].off, arr[i].len, arr[i].dst_off = int(r[0]), int(r[1]), int(r[2]) if len(r) > 2 else 0
+        return arr
+
+    def cover(self, ranges):
+        """xlz_xz_cover: the ascending indices of the blocks that [(off, n), ...] touch.  Host only."""
+        arr = self._ranges(ranges)
+        blocks = (ctypes.c_size_t * max(len(self.blocks), 1))()
+        n = ctypes.c_size_t()
+        st = N.lib().xlz_xz_cover(self._handle(), arr, len(ranges), blocks, len(self.blocks), ctypes.byref(n))
+        if st != OK:
+            raise LzmaError(st, "xlz_xz_cover")
+        return list(blocks[: n.value])
+
+    def _read(self, name, ctx, arr, n, dst, cap, verify):
+        copied = (ctypes.c_uint64 * max(n, 1))()
+        unverified = ctypes.c_size_t()
+        st = getattr(N.lib(), name)(ctx._h, self._handle(), arr, n, dst, cap, copied, 1 if verify else 0, ctypes.byref(unverified))
+        if st != OK:
+            raise LzmaError(st, name)
+        ctx.last_xz_unverified = unverified.value  # (on the context, like the statistics: the XzFile stays read-only)
+        return list(copied[:n])
+
+    def read_ranges(self, ctx, ranges, verify=True):
+        """xlz_xz_read of [(off, n), ...] -> list[bytes], each short where the file ends; ONE batch of the covering blocks"""
+        laid, at = [], 0
+        for off, n in ranges:
+            n = min(int(n), max(self.size - int(off), 0))
+            laid.append((off, n, at))
+            at += n
+        out = ctypes.create_string_buffer(max(at, 1))
+        copied = self._read("xlz_xz_read", ctx, self._ranges(laid), len(laid), ctypes.cast(out, ctypes.c_void_p), at, verify)
+        return [out[d:d + c] for (_, _, d), c in zip(laid, copied)]
+
+    def read(self, ctx, off, n, verify=True):
+        """bytes [off, off + n) of the decoded file, like pread: short at the end of the file, b"" behind it"""
+        return self.read_ranges(ctx, [(off, n)], verify=verify)[0]
+
+    def read_device(self, ctx, ranges_with_dst, dptr, cap, verify=True):
+        """xlz_xz_read_device: [(off, n, dst_off), ...] into `cap` bytes of device memory at the address `dptr` (on the
+        context's device), range i to dptr + dst_off -> the bytes written per range"""
+        return self._read("xlz_xz_read_device", ctx, self._ranges(ranges_with_dst), len(ranges_with_dst), ctypes.c_void_p(int(dptr)),
+                          int(cap), verify)
+
+    def read_tensor(self, ctx, off, n, verify=True, out=None):
+        """read_device of one range into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at
+        least the clipped length; ERR_OUT_CAP if smaller) or a new one -> the tensor cut to the bytes read"""
+        want = min(int(n), max(self.size - int(off), 0))
+
+        def read(ctx, data, dptr, cap, verify):
+            return self.read_device(ctx, [(off, want, 0)], dptr, cap, verify=verify)[0]
+        return _decode_tensor(read, want, ctx, None, verify, out)
+
+    def close(self):
+        if self._h:
+            N.lib().xlz_xz_close(self._h)
+            self._h = ctypes.c_void_p()
+        if getattr(self, "_held", False):
+            self._held = False
+            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

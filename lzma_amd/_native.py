@@ -58,6 +58,8 @@ EXPORTS = [
     "xlz_batch_digests", "xlz_decode_batch_digests", "xlz_sha256_plan", "xlz_ctx_last_sha256_stats",
     "xlz_batch_pack", "xlz_ctx_last_pack_stats", "xlz_xz_decode_device", "xlz_7z_decode_device",
     "xlz_bcj2_host", "xlz_batch_bcj2", "xlz_ctx_set_bcj2_mode", "xlz_ctx_bcj2_mode", "xlz_ctx_last_bcj2_stats", "xlz_7z_index_bcj2",
+    "xlz_xz_open", "xlz_xz_close", "xlz_xz_file_info", "xlz_xz_file_blocks", "xlz_xz_cover", "xlz_xz_read", "xlz_xz_read_device",
+    "xlz_ctx_last_xz_read_stats",
 ]
 
 
@@ -176,6 +178,15 @@ class XzBlock(ctypes.Structure):
         ("dict_size", ctypes.c_uint32),
         ("check_type", ctypes.c_uint32),
     ]
+
+
+class XzRange(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64)]
+
+
+class XzReadStats(ctypes.Structure):
+    _fields_ = [("ranges", ctypes.c_uint64), ("empty_ranges", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
+                ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64), ("copied_bytes", ctypes.c_uint64)]
 
 
 class Lzma2Unit(ctypes.Structure):
@@ -368,6 +379,16 @@ def lib():
         L.xlz_7z_index_bcj2.argtypes = [vp, vp, sz, ctypes.POINTER(SzFolder), sz, ctypes.POINTER(sz), ctypes.POINTER(SzSubstream), sz,
                                         ctypes.POINTER(sz), ctypes.POINTER(FilterStep), sz, ctypes.POINTER(sz), ctypes.POINTER(SzBcj2), sz,
                                         ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "xlz_xz_open"):  # (an older library loaded through XLZ_SO reads no byte ranges of a file)
+        L.xlz_xz_open.argtypes = [vp, sz, ctypes.POINTER(vp)]
+        L.xlz_xz_close.argtypes = [vp]
+        L.xlz_xz_close.restype = None
+        L.xlz_xz_file_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.xlz_xz_file_blocks.argtypes = [vp, ctypes.POINTER(XzBlock), sz]
+        L.xlz_xz_cover.argtypes = [vp, ctypes.POINTER(XzRange), sz, ctypes.POINTER(sz), sz, ctypes.POINTER(sz)]
+        L.xlz_xz_read.argtypes = [vp, vp, ctypes.POINTER(XzRange), sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
+        L.xlz_xz_read_device.argtypes = L.xlz_xz_read.argtypes
+        L.xlz_ctx_last_xz_read_stats.argtypes = [vp, ctypes.POINTER(XzReadStats)]
     _lib = L
     return L
 

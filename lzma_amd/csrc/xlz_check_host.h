@@ -11,12 +11,17 @@ void xlz_internal_check_stats_reset(xlz_ctx *ctx);
 void xlz_internal_check_stats_host(xlz_ctx *ctx, uint64_t ranges, uint64_t bytes);
 void xlz_internal_filter_stats_reset(xlz_ctx *ctx);
 void xlz_internal_sha256_stats_reset(xlz_ctx *ctx);
+void xlz_internal_pack_stats_reset(xlz_ctx *ctx);
+// what xlz_ctx_last_xz_read_stats reports: set by every xlz_xz_read / xlz_xz_read_device
+void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s);
 // xlz_decode_batch with what `post` asks for behind it: xlz_decode_batch_checked, _filtered and _digests are this
 int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post);
 
 // Where xlz_xz_decode_device / xlz_7z_decode_device want the decoded bytes: stream i of the call must produce exactly
 // want_out[i] bytes (and, where want_in is given, use exactly want_in[i] bytes of input), which go to d_dst + dst_off[i];
-// copies: bytes that go there from the host as they are (.7z Copy folders).
+// copies: bytes that go there from the host as they are (.7z Copy folders).  items (xlz_xz_read_device): the pack's table
+// spelled out -- any ranges of the streams, as xlz_batch_pack takes them -- instead of one whole stream per dst_off[i],
+// which is then not looked at.
 struct DeviceCopy {
     uint64_t dst_off;
     const uint8_t *src;
@@ -28,6 +33,9 @@ struct DeviceDest {
     const uint64_t *want_out = nullptr, *want_in = nullptr, *dst_off = nullptr;
     const DeviceCopy *copies = nullptr;
     size_t n_copies = 0;
+    const xlz_pack_item *items = nullptr;
+    size_t n_items = 0;
+    bool have_items = false;
     // .7z BCJ2 folders (bcj2 mode 1 / 2): no_pack[i] != 0 -- stream i is a sub-stream of one, it must still produce
     // want_out[i] bytes but is not packed; the folders are merged into d_dst behind the pack (items as xlz_batch_bcj2 takes
     // them, bcj2_res[] their outcomes, bcj2_mode 1: on the device, 2: on host threads)
@@ -42,6 +50,8 @@ struct DeviceDest {
 int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p);
 int xlz_internal_device_block_download(xlz_ctx *ctx, const void *p, uint8_t *dst, size_t bytes);
 void xlz_internal_device_block_release(xlz_ctx *ctx, void *p);
+// XLZ_OK: [p, p + cap) is device memory of the context's device, as far as the runtime tells (what xlz_batch_pack asks of d_dst)
+int xlz_internal_device_dst_ok(xlz_ctx *ctx, const void *p, size_t cap);
 void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx);
 // The device-destination form of xlz_internal_decode_batch (streams[i].out is NULL): one batch -- create, run, results,
 // the size checks above (a stream's own failure, then XLZ_ERR_RESULT) -- and behind it, all on the context's stream:

@@ -252,6 +252,7 @@ struct xlz_ctx {
     int filter_mode = 0;
     xlz_filter_stats last_filter = {};
     xlz_pack_stats last_pack = {}; // xlz_ctx_last_pack_stats (xlz_pack_dev.hip)
+    xlz_xz_read_stats last_xz_read = {}; // xlz_ctx_last_xz_read_stats (xlz_xz.hip)
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
     xlz_bcj2_stats last_bcj2 = {};
@@ -2406,6 +2407,16 @@ extern "C" int xlz_batch_pack(xlz_batch *b, const xlz_pack_item *items, size_t n
 }
 
 extern "C" int xlz_ctx_last_pack_stats(xlz_ctx *ctx, xlz_pack_stats *out) { return last_stats(ctx, &xlz_ctx::last_pack, out); }
+int xlz_internal_device_dst_ok(xlz_ctx *ctx, const void *p, size_t cap) { return ctx ? device_dst_ok(ctx, p, cap) : XLZ_ERR_BAD_ARG; }
+void xlz_internal_pack_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_pack, xlz_pack_stats{}, false); }
+
+// byte ranges of an .xz file (xlz_xz.hip: xlz_xz_read / xlz_xz_read_device)
+extern "C" int xlz_ctx_last_xz_read_stats(xlz_ctx *ctx, xlz_xz_read_stats *out) { return last_stats(ctx, &xlz_ctx::last_xz_read, out); }
+void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_xz_read = s;
+}
 
 // ---------------------------------------------------------------- BCJ2 folders ----
 namespace xlz {
@@ -3437,7 +3448,8 @@ int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size
 int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
                                const DeviceDest &dest)
 {
-    if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || !dest.dst_off))) return XLZ_ERR_BAD_ARG;
+    if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || (!dest.dst_off && !dest.have_items)))) return XLZ_ERR_BAD_ARG;
+    if (dest.have_items && ((!dest.items && dest.n_items) || dest.no_pack)) return XLZ_ERR_BAD_ARG;
     if (post_args(post, streams, n, true) != XLZ_OK) return XLZ_ERR_BAD_ARG;
     std::vector<size_t> of_streams, of_dest; // post.ranges by where their bytes lie
     for (size_t q = 0; q < post.n_ranges; q++) {
@@ -3451,7 +3463,9 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
             of_dest.push_back(q);
     }
     std::vector<xlz_pack_item> items;
-    for (size_t i = 0; i < n; i++)
+    if (dest.have_items)
+        items.assign(dest.items, dest.items + dest.n_items);
+    for (size_t i = 0; i < n && !dest.have_items; i++)
         if (!(dest.no_pack && dest.no_pack[i])) items.push_back(xlz_pack_item{i, 0, dest.want_out[i], dest.dst_off[i]});
     for (size_t k = 0; k < dest.n_copies; k++)
         if (dest.copies[k].dst_off > dest.cap || dest.copies[k].len > dest.cap - dest.copies[k].dst_off) return XLZ_ERR_BAD_ARG;

@@ -12,6 +12,7 @@
 // LZMA2 path is implemented: a block is one LZMA2 filter, or -- xlz_xz_index_chains, and xlz_xz_decode in
 // filter mode 1 -- one to three Delta / BCJ filters in front of it, which become filter steps of the
 // batch (xlz_filter_dev.hip).  ARM64, RISC-V and every other filter id: XLZ_ERR_UNSUPPORTED.
+// At the end: byte ranges of a file (xlz_xz_open / xlz_xz_read), a batch of the blocks that hold them (xlz_xz_cover.h).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include "xlz_check.h"
 #include "xlz_check_host.h"
 #include "xlz_filter_dev.h"
+#include "xlz_xz_cover.h"
 
 namespace {
 
@@ -402,4 +404,200 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     }
     *out_len = total;
     return XLZ_OK;
+}
+
+// ---------------------------------------------------------------- byte ranges of a file ----
+// The index parsed once (xlz_xz_open); a read (xlz_xz_read / xlz_xz_read_device) is ONE batch of the blocks that hold the
+// ranges' bytes -- xlz_xz_cover.h says which, and how every range is cut into pack items over them -- and behind it the
+// device's post-decode stage with that item list (xlz_internal_decode_device): filters, digests, pack.
+struct xlz_xz_file {
+    const uint8_t *file = nullptr; // borrowed: the caller keeps it alive
+    uint64_t size = 0;             // of the decoded file
+    std::vector<xlz_xz_block> blk;
+    std::vector<xlz_filter_step> steps; // ascending by stream (= block index), as xz_index lists them
+    std::vector<xlzcover::Extent> ext;  // (uncomp_off, uncomp_len) of blk[]
+};
+
+extern "C" int xlz_xz_open(const uint8_t *file, size_t len, xlz_xz_file **f)
+{
+    if (!f) return XLZ_ERR_BAD_ARG;
+    *f = nullptr;
+    size_t nb = 0, ns = 0;
+    uint64_t total = 0;
+    int st = xz_index(file, len, nullptr, 0, &nb, nullptr, 0, &ns, &total, true);
+    if (st != XLZ_OK) return st;
+    xlz_xz_file *h = new (std::nothrow) xlz_xz_file;
+    if (!h) return XLZ_ERR_DEVICE;
+    h->blk.resize(nb), h->steps.resize(ns);
+    st = xz_index(file, len, h->blk.data(), nb, &nb, h->steps.data(), ns, &ns, &total, true);
+    if (st != XLZ_OK) {
+        delete h;
+        return st;
+    }
+    h->file = file, h->size = total;
+    for (const xlz_xz_block &b : h->blk) h->ext.push_back(xlzcover::Extent{b.uncomp_off, b.uncomp_len});
+    *f = h;
+    return XLZ_OK;
+}
+
+extern "C" void xlz_xz_close(xlz_xz_file *f) { delete f; }
+
+extern "C" int xlz_xz_file_info(const xlz_xz_file *f, uint64_t *size, size_t *n_blocks, size_t *n_steps)
+{
+    if (!f) return XLZ_ERR_BAD_ARG;
+    if (size) *size = f->size;
+    if (n_blocks) *n_blocks = f->blk.size();
+    if (n_steps) *n_steps = f->steps.size();
+    return XLZ_OK;
+}
+
+extern "C" int xlz_xz_file_blocks(const xlz_xz_file *f, xlz_xz_block *blocks, size_t max_blocks)
+{
+    if (!f || (!blocks && max_blocks)) return XLZ_ERR_BAD_ARG;
+    std::copy_n(f->blk.begin(), std::min(max_blocks, f->blk.size()), blocks);
+    return f->blk.size() > max_blocks ? XLZ_ERR_OUT_CAP : XLZ_OK;
+}
+
+extern "C" int xlz_xz_cover(const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, size_t *blocks, size_t max_blocks, size_t *n_blocks)
+{
+    if (!f || (!ranges && n) || !n_blocks || (!blocks && max_blocks)) return XLZ_ERR_BAD_ARG;
+    std::vector<size_t> c;
+    xlzcover::cover(f->ext.data(), f->ext.size(), f->size, ranges, n, c);
+    *n_blocks = c.size();
+    std::copy_n(c.begin(), std::min(max_blocks, c.size()), blocks);
+    return c.size() > max_blocks && max_blocks ? XLZ_ERR_OUT_CAP : XLZ_OK;
+}
+
+// out: the host form (d_out == NULL) -- the pack goes to a staging block of the context's pool, where the ranges lie one
+// behind the other in the order of their destinations, and comes down from there in one copy
+static int xz_read(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, uint8_t *out, void *d_out, size_t out_cap,
+                   uint64_t *copied, int verify, size_t *unverified)
+{
+    // ---- the arguments: all of them before the context is used
+    if (!f || (!ranges && n)) return XLZ_ERR_BAD_ARG;
+    for (size_t i = 0; i < n && copied; i++) copied[i] = 0;
+    if (unverified) *unverified = 0;
+    xlzcover::Plan p;
+    if (!xlzcover::plan(f->ext.data(), f->ext.size(), f->size, ranges, n, out_cap, p)) return XLZ_ERR_BAD_ARG;
+    if (!ctx || (p.total && !out && !d_out)) return XLZ_ERR_BAD_ARG;
+    struct Run {
+        uint64_t staged, dst_off, len;
+    };
+    std::vector<Run> runs; // host form: staging bytes [staged, staged + len) -> out + dst_off
+    if (!d_out) {
+        std::vector<size_t> by_dst;
+        for (size_t i = 0; i < n; i++)
+            if (p.lens[i]) by_dst.push_back(i);
+        std::sort(by_dst.begin(), by_dst.end(), [&](size_t a, size_t b) { return ranges[a].dst_off < ranges[b].dst_off; });
+        std::vector<xlz_xz_range> staged(ranges, ranges + n);
+        uint64_t at = 0;
+        for (size_t i : by_dst) {
+            if (!runs.empty() && runs.back().dst_off + runs.back().len == ranges[i].dst_off)
+                runs.back().len += p.lens[i];
+            else
+                runs.push_back(Run{at, ranges[i].dst_off, p.lens[i]});
+            staged[i].dst_off = at, at += p.lens[i];
+        }
+        if (!xlzcover::plan(f->ext.data(), f->ext.size(), f->size, staged.data(), n, p.total, p)) return XLZ_ERR_BAD_ARG;
+    }
+    const size_t nc = p.blocks.size();
+    // what else refuses the call before anything is launched -- and before its statistics are made: a destination that is
+    // not the device's, a filter chain on a covering block in filter mode 0 (fs: the covering blocks' steps, stream = k)
+    if (d_out && p.total) {
+        const int ok = xlz_internal_device_dst_ok(ctx, d_out, out_cap);
+        if (ok != XLZ_OK) return ok;
+    }
+    std::vector<xlz_filter_step> fs;
+    for (size_t k = 0; k < nc; k++) {
+        auto it = std::lower_bound(f->steps.begin(), f->steps.end(), p.blocks[k], [](const xlz_filter_step &s, size_t b) { return s.stream < b; });
+        for (; it != f->steps.end() && it->stream == p.blocks[k]; ++it) fs.push_back(*it), fs.back().stream = k;
+    }
+    if (!fs.empty() && xlz_ctx_filter_mode(ctx) != 1) return XLZ_ERR_UNSUPPORTED;
+    xlz_xz_read_stats rs = {};
+    rs.ranges = n, rs.blocks = nc;
+    for (size_t i = 0; i < n; i++) rs.empty_ranges += !p.lens[i];
+    for (size_t k : p.blocks) rs.comp_bytes += f->blk[k].comp_len, rs.decoded_bytes += f->blk[k].uncomp_len;
+    xlz_internal_check_stats_reset(ctx), xlz_internal_sha256_stats_reset(ctx), xlz_internal_filter_stats_reset(ctx);
+    xlz_internal_pack_stats_reset(ctx), xlz_internal_xz_read_stats_set(ctx, rs);
+    if (!nc) return XLZ_OK; // (every range is empty)
+    // ---- the batch: the covering blocks, stream k = block p.blocks[k]; their checks
+    std::vector<xlz_stream_desc> d(nc);
+    std::vector<xlz_result> r(nc);
+    std::vector<uint64_t> want_out(nc), want_in(nc);
+    std::vector<xlz_check_range> cr;
+    bool dev_sha = false;
+    for (size_t k = 0; k < nc; k++) {
+        const xlz_xz_block &b = f->blk[p.blocks[k]];
+        memset(&d[k], 0, sizeof d[k]);
+        d[k].in = f->file + b.comp_off, d[k].in_len = (size_t)b.comp_len;
+        d[k].out_cap = (size_t)b.uncomp_len, d[k].format = XLZ_FMT_LZMA2_RAW, d[k].dict_size = b.dict_size;
+        want_out[k] = b.uncomp_len, want_in[k] = b.comp_len;
+        if (verify && (b.check_type == 1 || b.check_type == 4 || b.check_type == 10)) {
+            xlz_check_range c;
+            memset(&c, 0, sizeof c);
+            c.stream = k, c.off = 0, c.len = b.uncomp_len, c.kind = b.check_type;
+            cr.push_back(c);
+            dev_sha |= b.check_type == 10;
+        }
+    }
+    // (as xlz_xz_decode_device: the 32-byte form only where a block needs it, a CRC little-endian in its first bytes)
+    std::vector<uint64_t> got(dev_sha ? 0 : cr.size());
+    std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0);
+    const PostWork w = {fs.data(), fs.size(), cr.data(), cr.size(), dev_sha ? nullptr : got.data(), dev_sha ? xgot.data() : nullptr, true};
+    void *staging = nullptr;
+    if (!d_out) {
+        const int st = xlz_internal_device_block(ctx, (size_t)p.total, &staging);
+        if (st != XLZ_OK) return st;
+    }
+    DeviceDest dest;
+    dest.d_dst = d_out ? d_out : staging, dest.cap = d_out ? out_cap : (size_t)p.total;
+    dest.want_out = want_out.data(), dest.want_in = want_in.data();
+    dest.items = p.items.data(), dest.n_items = p.items.size(), dest.have_items = true;
+    int st = xlz_internal_decode_device(ctx, d.data(), nc, r.data(), w, dest);
+    size_t nu = 0;
+    for (size_t q = 0, k = 0; k < nc && st == XLZ_OK && verify; k++) {
+        const xlz_xz_block &b = f->blk[p.blocks[k]];
+        const uint8_t *c = f->file + b.check_off;
+        if (b.check_type == 0) continue;
+        if (b.check_type != 1 && b.check_type != 4 && b.check_type != 10) {
+            nu++; // reserved check types: not verified
+            continue;
+        }
+        uint8_t dg[32] = {};
+        if (dev_sha)
+            memcpy(dg, xgot[q].b, 32);
+        else
+            for (int j = 0; j < 8; j++) dg[j] = (uint8_t)(got[q] >> (8 * j));
+        q++;
+        if (memcmp(dg, c, check_size(b.check_type)) != 0) st = XLZ_ERR_RESULT;
+    }
+    if (st == XLZ_OK && runs.size() == 1) // (the destinations touch: straight into the caller's buffer)
+        st = xlz_internal_device_block_download(ctx, staging, out + runs[0].dst_off, (size_t)runs[0].len);
+    else if (st == XLZ_OK && !runs.empty()) { // ONE copy of the staging block, scattered on the host
+        std::vector<uint8_t> bounce((size_t)p.total);
+        st = xlz_internal_device_block_download(ctx, staging, bounce.data(), bounce.size());
+        for (size_t j = 0; j < runs.size() && st == XLZ_OK; j++) memcpy(out + runs[j].dst_off, bounce.data() + runs[j].staged, (size_t)runs[j].len);
+    }
+    if (staging) xlz_internal_device_block_release(ctx, staging);
+    if (st != XLZ_OK) return st;
+    for (size_t i = 0; i < n && copied; i++) copied[i] = p.lens[i];
+    if (unverified) *unverified = nu;
+    rs.copied_bytes = p.total;
+    xlz_internal_xz_read_stats_set(ctx, rs);
+    return XLZ_OK;
+}
+
+extern "C" int xlz_xz_read(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, uint8_t *out, size_t out_cap,
+                           uint64_t *copied, int verify, size_t *unverified)
+{
+    uint8_t none = 0; // (a read of nothing needs no destination)
+    return xz_read(ctx, f, ranges, n, out ? out : &none, nullptr, out ? out_cap : 0, copied, verify, unverified);
+}
+
+extern "C" int xlz_xz_read_device(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *ranges, size_t n, void *d_out, size_t out_cap,
+                                  uint64_t *copied, int verify, size_t *unverified)
+{
+    if (!d_out && out_cap) return XLZ_ERR_BAD_ARG;
+    uint8_t none = 0;
+    return xz_read(ctx, f, ranges, n, nullptr, d_out ? d_out : &none, d_out ? out_cap : 0, copied, verify, unverified);
 }
