@@ -714,6 +714,69 @@ typedef struct xlz_xz_read_stats {
 } xlz_xz_read_stats;
 int xlz_ctx_last_xz_read_stats(xlz_ctx *ctx, xlz_xz_read_stats *out);
 
+/* ---- many .xz files as ONE batch, each with a status of its own ---------
+ * What xz writes by default is one block per file, so a directory of small .xz files is a batch only across files.
+ * Every file has a window [dst_off, dst_off + dst_cap) in one destination; xlz_xz_many_layout (host only, no device) lays
+ * the windows out back to back: it parses every index -- results[i].status = what xlz_xz_index (chains == 0) or
+ * xlz_xz_index_chains (chains != 0) returns for file i --, sets dst_cap = the index's total (0 for a refused file) and
+ * dst_off = the next multiple of align (>= 1; 0: XLZ_ERR_BAD_ARG), and *total = the end of the last window.
+ * XLZ_ERR_OUT_CAP: the windows do not fit 64 bits.  `file` is borrowed for the call; the same file may be named twice.
+ *
+ * Per file: results[i].status and .unverified are what xlz_xz_decode (xlz_xz_decode_many) or xlz_xz_decode_device
+ * (xlz_xz_decode_many_device) returns for (file, len, a buffer of dst_cap bytes) ALONE on the same context with the same
+ * filter and check mode, and when that is XLZ_OK, out_len and the bytes at dst_off are what it produces.  That includes
+ * the order in which a file's failures are found: the index parse; XLZ_ERR_OUT_CAP when the index announces more than
+ * dst_cap; in the device form XLZ_ERR_UNSUPPORTED for a block of 4 GiB or more; the first block in file order whose own
+ * status is negative or whose sizes are not the index's (XLZ_ERR_RESULT); the first failed check (XLZ_ERR_RESULT).  A
+ * chain in filter mode 0 is XLZ_ERR_UNSUPPORTED, from the index parse.  A file that fails before the batch is made puts
+ * nothing into the batch (blocks = comp_bytes = 0).  An empty .xz file (no blocks) is a good file of out_len 0.
+ *
+ * The call itself returns XLZ_OK whenever it ran, however many files failed.  XLZ_ERR_BAD_ARG: ctx, files, results or
+ * the destination NULL (with n > 0 and out_cap > 0); a window that does not fit out_cap (no sum is formed unless it
+ * fits); two windows that share a byte (a window with dst_cap == 0 declares no byte, wherever its dst_off points) --
+ * these are tested before the context is used --; d_out that is not out_cap bytes of device memory of the context's
+ * device.  Such a call launches nothing, writes nothing -- results[] included -- and leaves every statistic as it was; so
+ * does n == 0, which is XLZ_OK.  Another negative status (XLZ_ERR_DEVICE): the batch could not run, and every
+ * results[i].status is that status too.
+ *
+ * Bytes outside every window are never written; inside the window of a good file, bytes behind out_len are not written;
+ * inside the window of a failed file the contents are unspecified.
+ *
+ * xlz_xz_decode_many_device is ONE batch (xlz_batch_create / run / results) over all blocks of all files that got that
+ * far, then on the device the filter steps (filter mode 1), the digests of every block with a known check (verify != 0;
+ * whatever the check mode, as xlz_xz_decode_device) and ONE pack; a block that failed or does not match its index is
+ * left out of these.  xlz_xz_decode_many goes the way of xlz_xz_decode -- the pipelined, sliced xlz_decode_batch with
+ * every block's output inside its file's window, sessions for blocks of 4 GiB and more -- and verifies where the
+ * context's check mode says.  The call holds the arena of all files (the device form: plus the destination); a set that
+ * does not fit device memory is the caller's to cut -- the layout's total tells.                                       */
+typedef struct xlz_xz_many_file {
+    const uint8_t *file; /* one whole .xz file, borrowed for the call                                    */
+    size_t len;
+    uint64_t dst_off;    /* its window [dst_off, dst_off + dst_cap) in the destination                   */
+    uint64_t dst_cap;
+} xlz_xz_many_file;
+typedef struct xlz_xz_many_result {
+    int32_t status;      /* what the single-file call would return for this file                         */
+    uint32_t unverified; /* its blocks with a reserved check type (0 unless status == XLZ_OK)            */
+    uint64_t out_len;    /* decoded bytes at dst_off; 0 unless status == XLZ_OK                          */
+    uint64_t blocks;     /* what it put into the batch: blocks ...                                       */
+    uint64_t comp_bytes; /* ... and their payload bytes                                                  */
+} xlz_xz_many_result;
+int xlz_xz_many_layout(xlz_xz_many_file *files, size_t n, int chains, uint64_t align, xlz_xz_many_result *results,
+                       uint64_t *total);
+int xlz_xz_decode_many(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, uint8_t *out, size_t out_cap, int verify,
+                       xlz_xz_many_result *results);
+int xlz_xz_decode_many_device(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, void *d_out, size_t out_cap,
+                              int verify, xlz_xz_many_result *results);
+/* Of the most recent xlz_xz_decode_many / xlz_xz_decode_many_device on `ctx` that ran (which also starts the check,
+ * SHA-256, filter and pack statistics over and fills them).                                                         */
+typedef struct xlz_xz_many_stats {
+    uint64_t files, failed_files; /* as given; of them with a status other than XLZ_OK                  */
+    uint64_t blocks, comp_bytes;  /* the batch: the blocks decoded and their payload bytes              */
+    uint64_t decoded_bytes;       /* the sum of out_len over the good files                             */
+} xlz_xz_many_stats;
+int xlz_ctx_last_xz_many_stats(xlz_ctx *ctx, xlz_xz_many_stats *out);
+
 /* ---- .7z container front-end ----------------------------
  * (The parser was written from 7-Zip's published format description.  It is exercised on archives
  * built from that description by tests/sevenzip_craft.py and their mutations AND on archives by an

@@ -174,6 +174,16 @@ class Context:
             raise LzmaError(st, "xlz_ctx_last_xz_read_stats")
         return {k: getattr(rs, k) for k, _ in N.XzReadStats._fields_}
 
+    def last_xz_many_stats(self):
+        """what the last xz_decode_many / xz_decode_many_into / xz_decode_many_device / xz_decode_many_tensor on this context
+        was made of (xlz_ctx_last_xz_many_stats) -> dict: files and failed_files, the blocks and comp_bytes of the one batch,
+        decoded_bytes = the sum over the good files"""
+        ms = N.XzManyStats()
+        st = N.lib().xlz_ctx_last_xz_many_stats(self._h, ctypes.byref(ms))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_xz_many_stats")
+        return {k: getattr(ms, k) for k, _ in N.XzManyStats._fields_}
+
     def set_bcj2_mode(self, mode):
         """what sevenzip_decode / sevenzip_decode_device do with BCJ2 folders (xlz_ctx_set_bcj2_mode): 0 refuse them (default),
         1 decode them and merge their streams on the device, 2 the same with the merge on host threads"""
@@ -1213,3 +1223,116 @@ class XzFile:
             self.close()
         except Exception:
             pass
+
+
+# ---- many .xz files as one batch (include/xlz.h: xlz_xz_many_layout / xlz_xz_decode_many / xlz_xz_decode_many_device) ----
+class _ManyFiles:
+    """an xlz_xz_many_file array over `datas` (bytes or contiguous buffers: bytearray, memoryview, mmap), every one borrowed
+    through the buffer protocol as XzFile borrows its file -- never copied -- and held until release()"""
+
+    def __init__(self, datas, windows=None):
+        self.n = len(datas)
+        if windows is not None and len(windows) != self.n:
+            raise ValueError("one window per file")
+        self.arr = (N.XzManyFile * max(self.n, 1))()
+        self.res = (N.XzManyResult * max(self.n, 1))()
+        self._views = (_PyBuffer * max(self.n, 1))()
+        self._held = 0
+        try:
+            for i, d in enumerate(datas):
+                ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(d), ctypes.byref(self._views[i]), 0)  # (raises: no buffer, not contiguous)
+                self._held = i + 1
+                self.arr[i].file, self.arr[i].len = self._views[i].buf, self._views[i].len
+                if windows is not None:
+                    self.arr[i].dst_off, self.arr[i].dst_cap = int(windows[i][0]), int(windows[i][1])
+        except Exception:
+            self.release()
+            raise
+
+    def layout(self, chains, align):
+        total = ctypes.c_uint64()
+        st = N.lib().xlz_xz_many_layout(self.arr, self.n, 1 if chains else 0, int(align), self.res, ctypes.byref(total))
+        if st != OK:
+            raise LzmaError(st, "xlz_xz_many_layout")
+        return total.value
+
+    def decode(self, name, ctx, dst, cap, verify):
+        st = getattr(N.lib(), name)(ctx._h, self.arr, self.n, dst, int(cap), 1 if verify else 0, self.res)
+        if st != OK:
+            raise LzmaError(st, name)
+        return [(self.res[i].status, self.res[i].out_len, self.res[i].unverified) for i in range(self.n)]
+
+    def release(self):
+        for i in range(self._held):
+            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._views[i]))
+        self._held = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+
+def _chains_of(chains, ctx):
+    return bool(chains) if chains is not None else ctx is not None and ctx.filter_mode() == 1
+
+
+def xz_many_layout(datas, chains=None, align=1, ctx=None):
+    """xlz_xz_many_layout: the windows of many .xz files back to back in one destination, each dst_off a multiple of
+    `align` -> ([(dst_off, dst_cap, status)], total); dst_cap is the index's total, 0 for a file whose index is refused
+    (status says why).  chains: accept Delta / BCJ filter chains (None: as ctx.filter_mode() says where a ctx is given,
+    otherwise no).  Host only.  Raises LzmaError(ERR_OUT_CAP) when the windows do not fit 64 bits."""
+    with _ManyFiles(datas) as m:
+        total = m.layout(_chains_of(chains, ctx), align)
+        return [(m.arr[i].dst_off, m.arr[i].dst_cap, m.res[i].status) for i in range(m.n)], total
+
+
+def xz_decode_many(ctx, datas, verify=True, max_size=None):
+    """xlz_xz_decode_many: many whole .xz files as ONE batch, into one host buffer laid out by xz_many_layout -> a list of
+    (bytes or None, status, unverified), one per file: what xz_decode gives for that file alone, except that a bad file is
+    its own status here and no exception.  max_size: refuse (ERR_OUT_CAP) a set whose indexes announce more in all.
+    Raises LzmaError only for what concerns the whole call."""
+    with _ManyFiles(datas) as m:
+        total = m.layout(_chains_of(None, ctx), 1)
+        if max_size is not None and total > max_size:
+            raise LzmaError(ERR_OUT_CAP, "xlz_xz_decode_many: the indexes announce %d bytes, max_size is %d" % (total, max_size))
+        out = ctypes.create_string_buffer(max(total, 1))
+        res = m.decode("xlz_xz_decode_many", ctx, ctypes.cast(out, ctypes.c_void_p), total, verify)
+        base = ctypes.addressof(out)
+        return [(ctypes.string_at(base + m.arr[i].dst_off, n) if st == OK else None, st, nu) for i, (st, n, nu) in enumerate(res)]
+
+
+def xz_decode_many_into(ctx, datas, out, windows, verify=True):
+    """xlz_xz_decode_many with the caller's buffer: file i goes to its window (dst_off, dst_cap) = windows[i] of `out` (a
+    writable buffer: bytearray, numpy array, ctypes array); windows must not overlap -> [(status, out_len, unverified)]"""
+    dst = out if isinstance(out, ctypes.Array) else (ctypes.c_char * memoryview(out).nbytes).from_buffer(out)
+    with _ManyFiles(datas, windows) as m:
+        return m.decode("xlz_xz_decode_many", ctx, ctypes.cast(dst, ctypes.c_void_p), ctypes.sizeof(dst), verify)
+
+
+def xz_decode_many_device(ctx, datas, dptr, cap, windows, verify=True):
+    """xlz_xz_decode_many_device: the same into `cap` bytes of device memory at the address `dptr` (on the context's device)
+    -- ONE batch over the blocks of all files, the filters, the checks and one pack on the device -> [(status, out_len,
+    unverified)] as xz_decode_device gives them for each file alone"""
+    with _ManyFiles(datas, windows) as m:
+        return m.decode("xlz_xz_decode_many_device", ctx, ctypes.c_void_p(int(dptr)), cap, verify)
+
+
+def xz_decode_many_tensor(ctx, datas, verify=True, align=1, out=None):
+    """xz_decode_many_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least
+    the layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(off, out_len, status, unverified)]): file i is
+    tensor[off:off + out_len] where its status is OK"""
+    import torch  # (only here: importing lzma_amd does not import torch)
+    dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
+    with _ManyFiles(datas) as m:
+        total = m.layout(_chains_of(None, ctx), align)
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
+        elif out.numel() < total:
+            raise LzmaError(ERR_OUT_CAP, "the indexes announce %d bytes, out holds %d" % (total, out.numel()))
+        torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
+        res = m.decode("xlz_xz_decode_many_device", ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), verify)
+        return out, [(m.arr[i].dst_off, n, st, nu) for i, (st, n, nu) in enumerate(res)]

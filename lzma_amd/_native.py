@@ -60,6 +60,7 @@ EXPORTS = [
     "xlz_bcj2_host", "xlz_batch_bcj2", "xlz_ctx_set_bcj2_mode", "xlz_ctx_bcj2_mode", "xlz_ctx_last_bcj2_stats", "xlz_7z_index_bcj2",
     "xlz_xz_open", "xlz_xz_close", "xlz_xz_file_info", "xlz_xz_file_blocks", "xlz_xz_cover", "xlz_xz_read", "xlz_xz_read_device",
     "xlz_ctx_last_xz_read_stats",
+    "xlz_xz_many_layout", "xlz_xz_decode_many", "xlz_xz_decode_many_device", "xlz_ctx_last_xz_many_stats",
 ]
 
 
@@ -187,6 +188,20 @@ class XzRange(ctypes.Structure):
 class XzReadStats(ctypes.Structure):
     _fields_ = [("ranges", ctypes.c_uint64), ("empty_ranges", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
                 ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64), ("copied_bytes", ctypes.c_uint64)]
+
+
+class XzManyFile(ctypes.Structure):
+    _fields_ = [("file", ctypes.c_void_p), ("len", ctypes.c_size_t), ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64)]
+
+
+class XzManyResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("unverified", ctypes.c_uint32), ("out_len", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
+                ("comp_bytes", ctypes.c_uint64)]
+
+
+class XzManyStats(ctypes.Structure):
+    _fields_ = [("files", ctypes.c_uint64), ("failed_files", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
+                ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64)]
 
 
 class Lzma2Unit(ctypes.Structure):
@@ -389,6 +404,12 @@ def lib():
         L.xlz_xz_read.argtypes = [vp, vp, ctypes.POINTER(XzRange), sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), i32, ctypes.POINTER(sz)]
         L.xlz_xz_read_device.argtypes = L.xlz_xz_read.argtypes
         L.xlz_ctx_last_xz_read_stats.argtypes = [vp, ctypes.POINTER(XzReadStats)]
+    if hasattr(L, "xlz_xz_decode_many"):  # (an older library loaded through XLZ_SO decodes one file per call)
+        L.xlz_xz_many_layout.argtypes = [ctypes.POINTER(XzManyFile), sz, i32, ctypes.c_uint64, ctypes.POINTER(XzManyResult),
+                                         ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_xz_decode_many.argtypes = [vp, ctypes.POINTER(XzManyFile), sz, vp, sz, i32, ctypes.POINTER(XzManyResult)]
+        L.xlz_xz_decode_many_device.argtypes = L.xlz_xz_decode_many.argtypes
+        L.xlz_ctx_last_xz_many_stats.argtypes = [vp, ctypes.POINTER(XzManyStats)]
     _lib = L
     return L
 

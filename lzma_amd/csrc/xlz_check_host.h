@@ -14,6 +14,8 @@ void xlz_internal_sha256_stats_reset(xlz_ctx *ctx);
 void xlz_internal_pack_stats_reset(xlz_ctx *ctx);
 // what xlz_ctx_last_xz_read_stats reports: set by every xlz_xz_read / xlz_xz_read_device
 void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s);
+// what xlz_ctx_last_xz_many_stats reports: set by every xlz_xz_decode_many / xlz_xz_decode_many_device that ran
+void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s);
 // xlz_decode_batch with what `post` asks for behind it: xlz_decode_batch_checked, _filtered and _digests are this
 int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post);
 
@@ -44,6 +46,11 @@ struct DeviceDest {
     size_t n_bcj2 = 0;
     xlz_bcj2_result *bcj2_res = nullptr;
     int bcj2_mode = 1;
+    // tolerant (xlz_xz_decode_many_device: ONE batch over the blocks of many files): a stream that failed, or that did not
+    // produce want_out[i] / use want_in[i], does not end the call.  It is left out of post.steps, of post.ranges (whose
+    // outputs stay as the caller set them) and of the pack; the caller reads results[] and folds them into its files.
+    // Not with items, no_pack or bcj2.
+    bool tolerant = false;
 };
 // a device block of at least `bytes` from the context's pool (xlz_7z_decode with a BCJ2 folder decodes into one), its
 // download into host memory once the context's stream has drained, and its return

@@ -34,6 +34,7 @@
 #include "xlz_filter_dev.h"
 #include "xlz_pack_dev.h"
 #include "xlz_bcj2_dev.h"
+#include "xlz_xz_many.h"
 
 using namespace xlz;
 
@@ -253,6 +254,7 @@ struct xlz_ctx {
     xlz_filter_stats last_filter = {};
     xlz_pack_stats last_pack = {}; // xlz_ctx_last_pack_stats (xlz_pack_dev.hip)
     xlz_xz_read_stats last_xz_read = {}; // xlz_ctx_last_xz_read_stats (xlz_xz.hip)
+    xlz_xz_many_stats last_xz_many = {}; // xlz_ctx_last_xz_many_stats (xlz_xz.hip)
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
     xlz_bcj2_stats last_bcj2 = {};
@@ -2417,6 +2419,13 @@ void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s)
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->last_xz_read = s;
 }
+// many .xz files as one batch (xlz_xz.hip: xlz_xz_decode_many / xlz_xz_decode_many_device)
+extern "C" int xlz_ctx_last_xz_many_stats(xlz_ctx *ctx, xlz_xz_many_stats *out) { return last_stats(ctx, &xlz_ctx::last_xz_many, out); }
+void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_xz_many = s;
+}
 
 // ---------------------------------------------------------------- BCJ2 folders ----
 namespace xlz {
@@ -3445,11 +3454,13 @@ int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size
 // xlz_check_host.h: the device-destination form, what xlz_xz_decode_device and xlz_7z_decode_device are built on.  One
 // batch on the context's stream, and behind it a line of stages that each publish what they did: the filters, the
 // digests of the ranges over streams, the pack, the BCJ2 merges, the digests of the ranges over the destination, the copies.
+static_assert(xlzmany::kMaxDeviceBlock == kMaxUnitBytes, "xlz_xz_many.h: which blocks the device form refuses before its batch");
 int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
                                const DeviceDest &dest)
 {
     if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || (!dest.dst_off && !dest.have_items)))) return XLZ_ERR_BAD_ARG;
     if (dest.have_items && ((!dest.items && dest.n_items) || dest.no_pack)) return XLZ_ERR_BAD_ARG;
+    if (dest.tolerant && (dest.have_items || dest.no_pack || dest.n_bcj2)) return XLZ_ERR_BAD_ARG;
     if (post_args(post, streams, n, true) != XLZ_OK) return XLZ_ERR_BAD_ARG;
     std::vector<size_t> of_streams, of_dest; // post.ranges by where their bytes lie
     for (size_t q = 0; q < post.n_ranges; q++) {
@@ -3492,14 +3503,26 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
             if (b->plans[i].oversize) st = XLZ_ERR_UNSUPPORTED; // (xlz_decode_batch decodes these as sessions, into host memory)
         if (st == XLZ_OK) st = xlz_batch_run(b);
         if (st == XLZ_OK) st = xlz_batch_results(b, results);
-        for (size_t i = 0; i < n && st == XLZ_OK; i++) // the first stream that failed, or that is not what its container says
+        auto as_announced = [&](size_t i) {
+            return results[i].status >= 0 && results[i].out_len == dest.want_out[i] && (!dest.want_in || results[i].in_consumed == dest.want_in[i]);
+        };
+        for (size_t i = 0; i < n && st == XLZ_OK && !dest.tolerant; i++) // the first stream that failed, or that is not what its container says
             if (results[i].status < 0)
                 st = results[i].status;
-            else if (results[i].out_len != dest.want_out[i] || (dest.want_in && results[i].in_consumed != dest.want_in[i]))
+            else if (!as_announced(i))
                 st = XLZ_ERR_RESULT;
+        std::vector<size_t> kept_steps; // tolerant: what is left of the steps, of the ranges over streams and of the pack
+        if (st == XLZ_OK && dest.tolerant) {
+            for (size_t q = 0; q < post.n_steps; q++)
+                if (as_announced((size_t)post.steps[q].stream)) kept_steps.push_back(q);
+            of_streams.erase(std::remove_if(of_streams.begin(), of_streams.end(), [&](size_t q) { return !as_announced((size_t)post.ranges[q].stream); }),
+                             of_streams.end());
+            items.erase(std::remove_if(items.begin(), items.end(), [&](const xlz_pack_item &it) { return !as_announced((size_t)it.stream); }), items.end());
+        }
         if (st == XLZ_OK && post.n_steps) {
             xlz_filter_stats flt = {};
-            st = batch_filter_run(b, post.steps, nullptr, post.n_steps, 0, stream, flt);
+            st = dest.tolerant ? batch_filter_run(b, post.steps, kept_steps.data(), kept_steps.size(), 0, stream, flt)
+                               : batch_filter_run(b, post.steps, nullptr, post.n_steps, 0, stream, flt);
             if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_filter, flt, true);
         }
         if (st == XLZ_OK) digests(of_streams, nullptr);

@@ -12,7 +12,8 @@
 // LZMA2 path is implemented: a block is one LZMA2 filter, or -- xlz_xz_index_chains, and xlz_xz_decode in
 // filter mode 1 -- one to three Delta / BCJ filters in front of it, which become filter steps of the
 // batch (xlz_filter_dev.hip).  ARM64, RISC-V and every other filter id: XLZ_ERR_UNSUPPORTED.
-// At the end: byte ranges of a file (xlz_xz_open / xlz_xz_read), a batch of the blocks that hold them (xlz_xz_cover.h).
+// At the end: byte ranges of a file (xlz_xz_open / xlz_xz_read), a batch of the blocks that hold them (xlz_xz_cover.h); and
+// many files as one batch with a status per file (xlz_xz_decode_many, xlz_xz_many.h).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -24,6 +25,7 @@
 #include "xlz_check_host.h"
 #include "xlz_filter_dev.h"
 #include "xlz_xz_cover.h"
+#include "xlz_xz_many.h"
 
 namespace {
 
@@ -600,4 +602,182 @@ extern "C" int xlz_xz_read_device(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_
     if (!d_out && out_cap) return XLZ_ERR_BAD_ARG;
     uint8_t none = 0;
     return xz_read(ctx, f, ranges, n, nullptr, d_out ? d_out : &none, d_out ? out_cap : 0, copied, verify, unverified);
+}
+
+// ---------------------------------------------------------------- many files, one batch ----
+// What xz writes by default is ONE block per file: a directory of small files is a batch only across files.  Every file is
+// parsed as xz_decode parses it; the blocks of all files that got that far are the streams of ONE call of the batch engine
+// (xlz_xz_many.h says which stream a (file, block) is), and what comes back per stream is folded into a verdict per file
+// -- the one xz_decode gives for that file alone --, so that a damaged file costs nobody else anything.
+extern "C" int xlz_xz_many_layout(xlz_xz_many_file *files, size_t n, int chains, uint64_t align, xlz_xz_many_result *results, uint64_t *total)
+{
+    if (!total || !align || ((!files || !results) && n)) return XLZ_ERR_BAD_ARG;
+    *total = 0;
+    std::vector<uint64_t> sizes(n, 0), off(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        size_t nb = 0, ns = 0;
+        uint64_t t = 0;
+        memset(&results[i], 0, sizeof results[i]);
+        results[i].status = xz_index(files[i].file, files[i].len, nullptr, 0, &nb, nullptr, 0, &ns, &t, chains != 0);
+        if (results[i].status == XLZ_OK) sizes[i] = t;
+    }
+    if (!xlzmany::layout(sizes.data(), n, align, off.data(), total)) {
+        *total = 0;
+        return XLZ_ERR_OUT_CAP;
+    }
+    for (size_t i = 0; i < n; i++) files[i].dst_off = off[i], files[i].dst_cap = sizes[i];
+    return XLZ_OK;
+}
+
+// out: the host form (every block's stream writes inside its file's window); d_out: the device form
+static int xz_many(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, uint8_t *out, void *d_out, bool device, size_t out_cap, int verify,
+                   xlz_xz_many_result *results)
+{
+    // ---- the arguments: all of them before the context is used, but the last
+    if (!n) return XLZ_OK;
+    if (!ctx || !files || !results || (out_cap && !(device ? d_out != nullptr : out != nullptr))) return XLZ_ERR_BAD_ARG;
+    if (!xlzmany::windows_ok(files, n, out_cap)) return XLZ_ERR_BAD_ARG;
+    if (device && out_cap) {
+        const int ok = xlz_internal_device_dst_ok(ctx, d_out, out_cap);
+        if (ok != XLZ_OK) return ok;
+    }
+    // ---- the files: index, room, (device form) blocks a unit cannot hold; what is left is the batch, stream = position in blk
+    const bool chains = xlz_ctx_filter_mode(ctx) == 1;
+    std::vector<xlz_xz_block> blk;
+    std::vector<xlz_filter_step> fs;
+    std::vector<uint8_t> in_batch(n, 0);
+    std::vector<size_t> n_blocks(n, 0);
+    std::vector<uint64_t> totals(n, 0);
+    xlz_xz_many_stats ms = {};
+    ms.files = n;
+    for (size_t i = 0; i < n; i++) {
+        const xlz_xz_many_file &f = files[i];
+        memset(&results[i], 0, sizeof results[i]);
+        size_t nb = 0, nfs = 0;
+        uint64_t total = 0;
+        int st = xz_index(f.file, f.len, nullptr, 0, &nb, nullptr, 0, &nfs, &total, chains);
+        if (st == XLZ_OK && total > f.dst_cap) st = XLZ_ERR_OUT_CAP;
+        if (st == XLZ_OK) {
+            const size_t b0 = blk.size(), s0 = fs.size();
+            blk.resize(b0 + nb), fs.resize(s0 + nfs);
+            st = xz_index(f.file, f.len, blk.data() + b0, nb, &nb, fs.data() + s0, nfs, &nfs, &total, chains);
+            for (size_t k = b0; k < blk.size() && st == XLZ_OK && device; k++) // (xlz_decode_batch decodes these as sessions, into host memory)
+                if (blk[k].comp_len > xlzmany::kMaxDeviceBlock || blk[k].uncomp_len > xlzmany::kMaxDeviceBlock) st = XLZ_ERR_UNSUPPORTED;
+            if (st != XLZ_OK) {
+                blk.resize(b0), fs.resize(s0);
+            } else {
+                for (size_t k = s0; k < fs.size(); k++) fs[k].stream += b0; // (block of the file -> stream of the batch)
+                in_batch[i] = 1, n_blocks[i] = nb, totals[i] = total;
+                results[i].blocks = nb;
+                for (size_t k = b0; k < blk.size(); k++) results[i].comp_bytes += blk[k].comp_len;
+                ms.blocks += nb, ms.comp_bytes += results[i].comp_bytes;
+            }
+        }
+        results[i].status = st;
+    }
+    const xlzmany::Map m = xlzmany::map_streams(in_batch.data(), n_blocks.data(), n);
+    const size_t S = blk.size(); // == m.file_of.size()
+    xlz_internal_check_stats_reset(ctx), xlz_internal_sha256_stats_reset(ctx), xlz_internal_filter_stats_reset(ctx);
+    xlz_internal_pack_stats_reset(ctx);
+    // ---- the batch: as xz_decode makes it for one file; where the checks come from as there (cmode)
+    std::vector<xlz_stream_desc> d(S);
+    std::vector<xlz_result> r(S);
+    std::vector<uint64_t> want_out(device ? S : 0), want_in(device ? S : 0), dst_off(device ? S : 0);
+    for (size_t s = 0; s < S; s++) {
+        // (inside the window: the index's total fits dst_cap; a block of no bytes has no place -- its window may be one of no
+        //  bytes, which may point anywhere)
+        const uint64_t at = blk[s].uncomp_len ? files[m.file_of[s]].dst_off + blk[s].uncomp_off : 0;
+        memset(&d[s], 0, sizeof d[s]);
+        memset(&r[s], 0, sizeof r[s]);
+        d[s].in = files[m.file_of[s]].file + blk[s].comp_off;
+        d[s].in_len = (size_t)blk[s].comp_len;
+        d[s].out = device ? nullptr : out + at;
+        d[s].out_cap = (size_t)blk[s].uncomp_len;
+        d[s].format = XLZ_FMT_LZMA2_RAW;
+        d[s].dict_size = blk[s].dict_size;
+        if (device) want_out[s] = blk[s].uncomp_len, want_in[s] = blk[s].comp_len, dst_off[s] = at;
+    }
+    const int cmode = !verify ? 0 : device ? 2 : xlz_ctx_check_mode(ctx);
+    const bool dev = cmode == 1 || cmode == 2;
+    bool dev_sha = false;
+    for (size_t s = 0; s < S && cmode == 2; s++) dev_sha |= blk[s].check_type == 10;
+    std::vector<xlz_check_range> cr;
+    std::vector<size_t> range_of(S, ~(size_t)0); // stream -> its range in cr
+    for (size_t s = 0; s < S && dev; s++)
+        if (blk[s].check_type == 1 || blk[s].check_type == 4 || (dev_sha && blk[s].check_type == 10)) {
+            xlz_check_range c;
+            memset(&c, 0, sizeof c);
+            c.stream = s, c.off = 0, c.len = blk[s].uncomp_len, c.kind = blk[s].check_type;
+            range_of[s] = cr.size();
+            cr.push_back(c);
+        }
+    // (the 32-byte form only where a block needs it, a CRC little-endian in its first bytes: as xz_decode)
+    std::vector<uint64_t> got(dev_sha ? 0 : cr.size(), 0);
+    std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0, xlz_digest{});
+    const PostWork w = {fs.data(), fs.size(), cr.data(), cr.size(), !cr.empty() && !dev_sha ? got.data() : nullptr,
+                        !cr.empty() && dev_sha ? xgot.data() : nullptr, true};
+    int st = XLZ_OK;
+    if (S && device) {
+        DeviceDest dest;
+        dest.d_dst = d_out, dest.cap = out_cap, dest.want_out = want_out.data(), dest.want_in = want_in.data(), dest.dst_off = dst_off.data();
+        dest.tolerant = true;
+        st = xlz_internal_decode_device(ctx, d.data(), S, r.data(), w, dest);
+    } else if (S)
+        st = xlz_internal_decode_batch(ctx, d.data(), S, r.data(), w);
+    if (st != XLZ_OK) { // the batch could not run: nobody has a result
+        for (size_t i = 0; i < n; i++) results[i].status = st;
+        ms.failed_files = n;
+        xlz_internal_xz_many_stats_set(ctx, ms);
+        return st;
+    }
+    // ---- per stream: what the block did, what its check says; per file: the fold
+    std::vector<int32_t> block_st(S);
+    std::vector<uint8_t> check(S, xlzmany::kCheckGood);
+    for (size_t s = 0; s < S; s++) block_st[s] = xlzmany::block_status(r[s].status, r[s].out_len, r[s].in_consumed, blk[s].uncomp_len, blk[s].comp_len);
+    if (verify)
+        xlzpost::parallel_for(S, xlzpost::host_thread_cap(16), [&](size_t s) {
+            if (block_st[s] < 0) return;
+            const xlz_xz_block &b = blk[s];
+            const uint8_t *p = device ? nullptr : d[s].out; // (the device form: every check below is the device's)
+            const uint8_t *c = files[m.file_of[s]].file + b.check_off;
+            uint8_t dg[32] = {};
+            if (range_of[s] != ~(size_t)0 && dev_sha)
+                memcpy(dg, xgot[range_of[s]].b, 32);
+            else if (range_of[s] != ~(size_t)0)
+                for (int j = 0; j < 8; j++) dg[j] = (uint8_t)(got[range_of[s]] >> (8 * j));
+            else if (b.check_type == 1)
+                for (uint32_t v = crc32(p, (size_t)b.uncomp_len), j = 0; j < 4; j++) dg[j] = (uint8_t)(v >> (8 * j));
+            else if (b.check_type == 4)
+                for (uint64_t v = crc64(p, (size_t)b.uncomp_len), j = 0; j < 8; j++) dg[j] = (uint8_t)(v >> (8 * j));
+            else if (b.check_type == 10)
+                xlzcheck::sha256(p, (size_t)b.uncomp_len, dg);
+            if (b.check_type == 1 || b.check_type == 4 || b.check_type == 10)
+                check[s] = memcmp(dg, c, check_size(b.check_type)) != 0 ? xlzmany::kCheckFailed : xlzmany::kCheckGood;
+            else if (b.check_type != 0)
+                check[s] = xlzmany::kCheckUnverified; // reserved check types: not verified
+        });
+    for (size_t s = 0; s < S && verify && dev && !dev_sha; s++) // (check mode 1: the SHA-256 blocks stayed with the host threads above)
+        if (blk[s].check_type == 10 && block_st[s] >= 0) xlz_internal_check_stats_host(ctx, 1, blk[s].uncomp_len);
+    for (size_t i = 0; i < n; i++) {
+        if (in_batch[i]) {
+            const xlzmany::Verdict v = xlzmany::fold(block_st.data(), check.data(), m.first[i], m.count[i], verify != 0);
+            results[i].status = v.status, results[i].unverified = v.unverified;
+            if (v.status == XLZ_OK) results[i].out_len = totals[i], ms.decoded_bytes += totals[i];
+        }
+        ms.failed_files += results[i].status != XLZ_OK;
+    }
+    xlz_internal_xz_many_stats_set(ctx, ms);
+    return XLZ_OK;
+}
+
+extern "C" int xlz_xz_decode_many(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, uint8_t *out, size_t out_cap, int verify,
+                                  xlz_xz_many_result *results)
+{
+    return xz_many(ctx, files, n, out, nullptr, false, out_cap, verify, results);
+}
+
+extern "C" int xlz_xz_decode_many_device(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, void *d_out, size_t out_cap, int verify,
+                                         xlz_xz_many_result *results)
+{
+    return xz_many(ctx, files, n, nullptr, d_out, true, out_cap, verify, results);
 }
