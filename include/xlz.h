@@ -791,8 +791,9 @@ int xlz_ctx_last_xz_many_stats(xlz_ctx *ctx, xlz_xz_many_stats *out);
  * xlz_7z_decode also takes folders that are a line of Delta / BCJ filters behind one LZMA / LZMA2
  * coder (xlz_7z_index_chains) and undoes the filters on the device between decode and CRC; in bcj2
  * mode 1 / 2 (xlz_ctx_set_bcj2_mode) also BCJ2 folders (xlz_7z_index_bcj2), merged on the device.  Other
- * coder graphs, encryption and external / multi-volume layouts are reported as unsupported.  File names are not parsed: the
- * output is the folders' bytes back to back = the archive's files back to back.                */
+ * coder graphs, encryption and external / multi-volume layouts are reported as unsupported.  xlz_7z_decode and its kin do not
+ * look at file names: their output is the folders' bytes back to back = the archive's files back to back.  The file table
+ * (names, sizes, times) and the extraction of chosen files are xlz_7z_open / xlz_7z_extract below.  */
 enum { XLZ_7Z_UNSUPPORTED = 0, XLZ_7Z_LZMA = 1, XLZ_7Z_LZMA2 = 2, XLZ_7Z_COPY = 3,
        XLZ_7Z_BCJ2 = 4 /* xlz_7z_index_bcj2 only */ };
 typedef struct xlz_7z_folder {
@@ -876,6 +877,127 @@ int xlz_7z_decode_device(xlz_ctx *ctx, const uint8_t *file, size_t len, void *d_
 /* the same over several contexts (one per GPU; encoded headers are decoded on the first)         */
 int xlz_7z_decode_multi(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, size_t len, uint8_t *out,
                         size_t out_cap, uint64_t *out_len, int verify, size_t *unverified);
+
+/* ---- the files of a .7z archive: the table, and chosen files as ONE batch ----------------
+ * xlz_7z_open parses the streams as xlz_7z_index_bcj2 does -- the same status for every input, the same folder list --
+ * and then the FilesInfo section (7zFormat.txt): names, empty-stream / empty-file / anti bits, modification times and
+ * Windows attributes; other properties are skipped.  ctx may be NULL for a plain header; an encoded header is decoded
+ * on the device as ever.  An archive without FilesInfo has no entries; one whose FilesInfo has no names has entries
+ * with empty names.  Refused: External data (XLZ_ERR_UNSUPPORTED); a property whose data does not fill, or overruns,
+ * its announced size, a name pool that does not hold exactly one terminated name per entry, a number of entries with a
+ * stream that is not the number of substreams, a byte behind the StreamsInfo that is neither FilesInfo nor the header's end
+ * mark, a FilesInfo that the end mark does not follow (XLZ_ERR_RESULT).  These are all that xlz_7z_open refuses beyond
+ * xlz_7z_index_bcj2, which never reads behind the StreamsInfo.  xlz_7z_index* and xlz_7z_decode* keep ignoring
+ * FilesInfo: an archive with a broken one still decodes through them.  The handle BORROWS `file` until xlz_7z_close
+ * and never changes after open: any number of threads and contexts may use one at once.  Open, close, info, entries,
+ * folders, cover and layout are host only.
+ *
+ * Names are converted from UTF-16LE to UTF-8 (an unpaired surrogate becomes U+FFFD) and handed out AS STORED, each
+ * NUL-terminated in one pool: no separator is normalised, no ".." removed, nothing is made relative.  The library
+ * writes no files; A CALLER THAT DOES MUST NOT TRUST A NAME AS A PATH.
+ *
+ * The entries that have a stream map, in order, onto the substreams of the folders: entry -> (folder, folder_off, size,
+ * crc).  An entry without a stream is a directory when it is not marked as an empty file.
+ *
+ * xlz_7z_cover: for the wanted entries, the ascending, duplicate-free folders that hold bytes of them, and how much of
+ * each must be decoded.  With P = the largest folder_off + size over the wanted entries of a folder: an LZMA folder and
+ * an LZMA2 folder of one unit are cut at P (decode_len = P, the input whole); an LZMA2 folder of several units
+ * (xlz_lzma2_units) is cut at the end of the unit that holds byte P - 1, its INPUT too (in_len), so that it is still
+ * launched unit-parallel; a folder with filter steps, a Copy folder, a BCJ2 folder and an unsupported one are never cut.
+ * items may be NULL with max_items 0 to obtain the count; XLZ_ERR_OUT_CAP when a non-zero capacity is too small (the
+ * count is still set).  xlz_7z_extract_layout sets wants[i].dst_cap = the entry's size and dst_off = the next multiple of
+ * align (>= 1; 0: XLZ_ERR_BAD_ARG) behind the window before, *total = the end of the last window (XLZ_ERR_OUT_CAP: the
+ * windows do not fit 64 bits; XLZ_ERR_BAD_ARG: an entry index outside the table).
+ *
+ * xlz_7z_extract_device: ONE batch of the covering folders (xlz_batch_create / run / results), then on the device the
+ * filter steps (filter mode 1), the CRC32 of every wanted entry that has one as a range over its folder's stream
+ * (verify != 0, whatever the check mode) and ONE pack of the wanted entries' bytes into their windows.  Entries of Copy
+ * folders are uploaded from the file; their CRC is computed on the host over the file's bytes.  xlz_7z_extract: the
+ * same through a staging block of the context's pool that holds the wanted sizes back to back, one download, and a
+ * scatter into the windows; the block stays with the context until xlz_ctx_trim.
+ *
+ * Per wanted entry, in this order: XLZ_ERR_OUT_CAP -- dst_cap is smaller than the entry (the entry then asks nothing of
+ * its folder); XLZ_ERR_UNSUPPORTED -- the folder's method is unsupported, it is a filter chain on a context in filter
+ * mode 0, it is a BCJ2 folder (in any bcj2 mode), or the folder or its packed stream is 4 GiB or more, whatever its cut; the
+ * folder's stream did not end as expected -- a whole folder: a status >= 0 with exactly its size; a folder cut by
+ * capacity: XLZ_ERR_OUT_CAP with exactly decode_len bytes; a folder cut at a unit: XLZ_ERR_UNEXPECTED_EOF with exactly
+ * decode_len bytes and all of in_len used --: the stream's own status where that is another negative one, else
+ * XLZ_ERR_RESULT, for EVERY wanted entry of that folder (such a stream is left out of steps, ranges and pack);
+ * XLZ_ERR_RESULT -- the entry's CRC differs: only that entry fails.  An entry without bytes is XLZ_OK with out_len 0,
+ * whatever its window.  unverified = 1: verify is on and the entry has bytes but no CRC.  The same entry may be wanted
+ * twice, into two windows.
+ *
+ * INVARIANT: an entry that is XLZ_OK in a call is XLZ_OK with the same bytes when it is extracted alone -- alone its
+ * folder is cut no later.  The reverse does not hold: damage behind a folder's cut is not seen.
+ *
+ * The call returns XLZ_OK whenever it ran.  XLZ_ERR_BAD_ARG: NULL arguments with n > 0; an entry index outside the table;
+ * a window of an entry with bytes that does not fit out_cap; two such windows that share a byte (these are tested
+ * before the context is used; the window of an entry without bytes declares nothing); d_out that is not out_cap bytes of
+ * device memory of the context's device.  Such a call launches nothing, writes nothing -- results[] included -- and
+ * leaves every statistic as it was; an empty want list launches nothing either and is XLZ_OK.  Another negative status
+ * (XLZ_ERR_DEVICE): the batch could not run, and every results[i].status is that status.  Bytes outside every window are
+ * never written; inside the window of a good entry nothing behind out_len is written.                                 */
+typedef struct xlz_7z_archive xlz_7z_archive;
+#define XLZ_7Z_NO_FOLDER (~(uint64_t)0)
+enum { XLZ_7Z_ENTRY_HAS_STREAM = 1, XLZ_7Z_ENTRY_HAS_CRC = 2, XLZ_7Z_ENTRY_IS_DIR = 4, XLZ_7Z_ENTRY_IS_ANTI = 8,
+       XLZ_7Z_ENTRY_HAS_MTIME = 16, XLZ_7Z_ENTRY_HAS_ATTRIBUTES = 32 };
+typedef struct xlz_7z_entry {  /* 64 bytes */
+    uint64_t size;       /* 0 without a stream                                                             */
+    uint64_t folder;     /* index into the folders; XLZ_7Z_NO_FOLDER without a stream                      */
+    uint64_t folder_off; /* where its bytes begin inside the folder's decoded bytes                        */
+    uint64_t substream;  /* index into the substreams of xlz_7z_index*; XLZ_7Z_NO_FOLDER without a stream  */
+    uint64_t mtime;      /* raw FILETIME: 100 ns since 1601-01-01 UTC (XLZ_7Z_ENTRY_HAS_MTIME)             */
+    uint64_t name_off;   /* into the name pool: UTF-8, NUL-terminated                                      */
+    uint32_t name_len;   /* bytes, without the NUL                                                         */
+    uint32_t crc;        /* CRC32 of its bytes (XLZ_7Z_ENTRY_HAS_CRC)                                      */
+    uint32_t attributes; /* Windows attributes (XLZ_7Z_ENTRY_HAS_ATTRIBUTES)                               */
+    uint32_t flags;      /* XLZ_7Z_ENTRY_*                                                                 */
+} xlz_7z_entry;
+typedef struct xlz_7z_want {
+    uint64_t entry;      /* index into the entries                                                         */
+    uint64_t dst_off;    /* its window [dst_off, dst_off + dst_cap) in the destination                     */
+    uint64_t dst_cap;
+} xlz_7z_want;
+typedef struct xlz_7z_file_result {
+    int32_t status;
+    uint32_t unverified; /* 1: verify was on, the entry has bytes and no CRC (0 unless status == XLZ_OK)   */
+    uint64_t out_len;    /* bytes at dst_off; 0 unless status == XLZ_OK                                    */
+} xlz_7z_file_result;
+typedef struct xlz_7z_cover_item {
+    uint64_t folder;
+    uint64_t decode_len; /* how much of the folder's bytes the batch is asked for                          */
+    uint64_t in_len;     /* how much of its packed stream goes into the batch                              */
+} xlz_7z_cover_item;
+int xlz_7z_open(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_archive **a);
+void xlz_7z_close(xlz_7z_archive *a);
+/* every pointer but `a` may be NULL.  name_bytes: the size of the name pool; total_size: the sum of the entries' sizes  */
+int xlz_7z_archive_info(const xlz_7z_archive *a, size_t *n_entries, size_t *n_folders, size_t *name_bytes,
+                        uint64_t *total_size);
+/* at most max_entries entries and names_cap bytes of the pool are copied; XLZ_ERR_OUT_CAP: there are more of either   */
+int xlz_7z_archive_entries(const xlz_7z_archive *a, xlz_7z_entry *entries, size_t max_entries, char *names,
+                           size_t names_cap);
+/* the folders as xlz_7z_index_bcj2 lists them; XLZ_ERR_OUT_CAP: more than max_folders                                  */
+int xlz_7z_archive_folders(const xlz_7z_archive *a, xlz_7z_folder *folders, size_t max_folders);
+int xlz_7z_cover(const xlz_7z_archive *a, const uint64_t *entries, size_t n, xlz_7z_cover_item *items, size_t max_items,
+                 size_t *n_items);
+int xlz_7z_extract_layout(const xlz_7z_archive *a, xlz_7z_want *wants, size_t n, uint64_t align, uint64_t *total);
+int xlz_7z_extract(xlz_ctx *ctx, const xlz_7z_archive *a, const xlz_7z_want *wants, size_t n, uint8_t *out,
+                   size_t out_cap, int verify, xlz_7z_file_result *results);
+int xlz_7z_extract_device(xlz_ctx *ctx, const xlz_7z_archive *a, const xlz_7z_want *wants, size_t n, void *d_out,
+                          size_t out_cap, int verify, xlz_7z_file_result *results);
+/* Of the most recent xlz_7z_extract / xlz_7z_extract_device on `ctx` that ran: one that passed its argument tests and had a
+ * want list that is not empty.  Such a call starts the check, filter and pack statistics over, fills them, and publishes
+ * these at its end -- also when the device then failed it (XLZ_ERR_DEVICE: failed_entries == entries, copied_bytes 0). */
+typedef struct xlz_7z_extract_stats {
+    uint64_t entries, empty_entries; /* as wanted; of them without bytes                                  */
+    uint64_t failed_entries;         /* with a status other than XLZ_OK                                   */
+    uint64_t folders, comp_bytes;    /* the cover of the entries that asked for their folder (Copy folders
+                                        included), and what goes in of their packed streams (in_len)       */
+    uint64_t decoded_bytes;          /* what the batch was asked to decode of them (the sum of decode_len) */
+    uint64_t folder_bytes;           /* their full sizes: folder_bytes - decoded_bytes is what the cuts saved */
+    uint64_t copied_bytes;           /* the sum of out_len                                                */
+} xlz_7z_extract_stats;
+int xlz_ctx_last_7z_extract_stats(xlz_ctx *ctx, xlz_7z_extract_stats *out);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ Decode* helpers) on top of the C ABI in include/xlz.h.  All decoding happens in
 hand-written HIP kernels (lzma_amd/csrc); this package only marshals buffers.
 It fails loudly when libxlz.so or a GPU is missing -- there is no CPU fallback.
 """
+import collections
 import ctypes
 
 from . import _native as N
@@ -190,6 +191,16 @@ class Context:
         st = N.lib().xlz_ctx_set_bcj2_mode(self._h, int(mode))
         if st != OK:
             raise LzmaError(st, "xlz_ctx_set_bcj2_mode")
+
+    def last_7z_extract_stats(self):
+        """of the most recent SevenZipFile extraction on this context that ran: entries, empty_entries, failed_entries,
+        folders, comp_bytes, decoded_bytes (what the batch was asked to decode), folder_bytes (the covering folders' full
+        sizes: the difference is what the cuts saved), copied_bytes"""
+        s = N.SzExtractStats()
+        st = N.lib().xlz_ctx_last_7z_extract_stats(self._h, ctypes.byref(s))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_7z_extract_stats")
+        return {f: getattr(s, f) for f, _ in N.SzExtractStats._fields_}
 
     def bcj2_mode(self):
         L = N.lib()
@@ -1207,6 +1218,175 @@ class XzFile:
     def close(self):
         if self._h:
             N.lib().xlz_xz_close(self._h)
+            self._h = ctypes.c_void_p()
+        if getattr(self, "_held", False):
+            self._held = False
+            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the files of a .7z archive (include/xlz.h: xlz_7z_open / xlz_7z_cover / xlz_7z_extract / xlz_7z_extract_device) ----
+SevenZipEntry = collections.namedtuple("SevenZipEntry", "name size is_dir has_stream crc mtime attributes folder folder_off is_anti")
+
+
+class SevenZipFile:
+    """The file table of one .7z archive (xlz_7z_open) and the extraction of chosen files as ONE batch: the folders that hold
+    them, each decoded only as far as the last wanted file reaches.  `data` is bytes or any contiguous buffer; it is
+    borrowed through the buffer protocol, never copied, and held until close().  ctx: needed only for an archive whose
+    header is encoded (it is decoded on the device).  Raises LzmaError as sevenzip_index_bcj2 does, and for a FilesInfo
+    section the parser refuses.  Names are AS STORED in the archive: do not trust one as a path.  Read-only once made; a
+    context manager; close() may be repeated."""
+
+    def __init__(self, data, ctx=None):
+        self._h = ctypes.c_void_p()
+        self._view = _PyBuffer()
+        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:
+            raise TypeError("SevenZipFile needs bytes or a contiguous buffer")
+        self._held = True
+        try:
+            L = N.lib()
+            st = L.xlz_7z_open(ctx._h if ctx is not None else None, ctypes.c_void_p(self._view.buf), self._view.len, ctypes.byref(self._h))
+            if st != OK:
+                self._h = ctypes.c_void_p()
+                raise LzmaError(st, "xlz_7z_open")
+            ne, nf, nb, total = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64()
+            L.xlz_7z_archive_info(self._h, ctypes.byref(ne), ctypes.byref(nf), ctypes.byref(nb), ctypes.byref(total))
+            ents = (N.SzEntry * max(ne.value, 1))()
+            pool = ctypes.create_string_buffer(max(nb.value, 1))
+            st = L.xlz_7z_archive_entries(self._h, ents, ne.value, ctypes.cast(pool, ctypes.c_void_p), nb.value)
+            if st != OK:
+                raise LzmaError(st, "xlz_7z_archive_entries")
+            fo = (N.SzFolder * max(nf.value, 1))()
+            st = L.xlz_7z_archive_folders(self._h, fo, nf.value)
+            if st != OK:
+                raise LzmaError(st, "xlz_7z_archive_folders")
+        except Exception:
+            self.close()
+            raise
+        self.total_size = total.value
+        raw = pool.raw
+        self.entries = []
+        for i in range(ne.value):
+            x = ents[i]
+            has_stream = bool(x.flags & N.SZ_ENTRY_HAS_STREAM)
+            mtime = (x.mtime - 116444736000000000) / 1e7 if x.flags & N.SZ_ENTRY_HAS_MTIME else None  # FILETIME -> Unix seconds
+            self.entries.append(SevenZipEntry(
+                raw[x.name_off:x.name_off + x.name_len].decode("utf-8"), x.size, bool(x.flags & N.SZ_ENTRY_IS_DIR), has_stream,
+                x.crc if x.flags & N.SZ_ENTRY_HAS_CRC else None, mtime, x.attributes if x.flags & N.SZ_ENTRY_HAS_ATTRIBUTES else None,
+                x.folder if has_stream else None, x.folder_off if has_stream else None, bool(x.flags & N.SZ_ENTRY_IS_ANTI)))
+        fields = [f for f, _ in N.SzFolder._fields_ if f != "reserved"]
+        self.folders = [{f: getattr(fo[i], f) for f in fields} for i in range(nf.value)]
+        self.names = [e.name for e in self.entries]
+
+    def _handle(self):
+        if not self._h:
+            raise LzmaError(ERR_CLOSED, "SevenZipFile is closed")
+        return self._h
+
+    def index(self, which):
+        """an entry's index from an index or a name (the first entry of that name)"""
+        if isinstance(which, str):
+            try:
+                return self.names.index(which)
+            except ValueError:
+                raise KeyError(which)
+        return int(which)
+
+    def _list(self, which):
+        return [self.index(w) for w in ([which] if isinstance(which, (int, str)) else which)]
+
+    def cover(self, which):
+        """xlz_7z_cover: [(folder, decode_len, in_len)] for the wanted entries (indices or names).  Host only."""
+        idx = self._list(which)
+        arr = (ctypes.c_uint64 * max(len(idx), 1))(*idx)
+        items = (N.SzCoverItem * max(len(self.folders), 1))()
+        n = ctypes.c_size_t()
+        st = N.lib().xlz_7z_cover(self._handle(), arr, len(idx), items, len(self.folders), ctypes.byref(n))
+        if st != OK:
+            raise LzmaError(st, "xlz_7z_cover")
+        return [(items[i].folder, items[i].decode_len, items[i].in_len) for i in range(n.value)]
+
+    def _wants(self, wants):
+        arr = (N.SzWant * max(len(wants), 1))()
+        for i, w in enumerate(wants):
+            arr[i].entry, arr[i].dst_off, arr[i].dst_cap = int(w[0]), int(w[1]), int(w[2])
+        return arr
+
+    def layout(self, which, align=1):
+        """xlz_7z_extract_layout: windows of the wanted entries back to back -> ([(entry, dst_off, dst_cap)], total)"""
+        idx = self._list(which)
+        arr = self._wants([(i, 0, 0) for i in idx])
+        total = ctypes.c_uint64()
+        st = N.lib().xlz_7z_extract_layout(self._handle(), arr, len(idx), int(align), ctypes.byref(total))
+        if st != OK:
+            raise LzmaError(st, "xlz_7z_extract_layout")
+        return [(arr[i].entry, arr[i].dst_off, arr[i].dst_cap) for i in range(len(idx))], total.value
+
+    def _extract(self, name, ctx, wants, dst, cap, verify):
+        res = (N.SzFileResult * max(len(wants), 1))()
+        st = getattr(N.lib(), name)(ctx._h, self._handle(), self._wants(wants), len(wants), dst, int(cap), 1 if verify else 0, res)
+        if st != OK:
+            raise LzmaError(st, name)
+        return [(res[i].status, res[i].out_len, res[i].unverified) for i in range(len(wants))]
+
+    def extract_into(self, ctx, wants, out, verify=True):
+        """xlz_7z_extract with the caller's buffer: wants = [(entry, dst_off, dst_cap)] into `out` (a writable buffer); the
+        windows of entries with bytes must not overlap -> [(status, out_len, unverified)]"""
+        dst = out if isinstance(out, ctypes.Array) else (ctypes.c_char * memoryview(out).nbytes).from_buffer(out)
+        return self._extract("xlz_7z_extract", ctx, wants, ctypes.cast(dst, ctypes.c_void_p), ctypes.sizeof(dst), verify)
+
+    def extract_device(self, ctx, wants, dptr, cap, verify=True):
+        """xlz_7z_extract_device: the same into `cap` bytes of device memory at the address `dptr` (on the context's device)"""
+        return self._extract("xlz_7z_extract_device", ctx, wants, ctypes.c_void_p(int(dptr)), cap, verify)
+
+    def extract(self, ctx, which, verify=True):
+        """the wanted entries (indices or names) as ONE batch -> a list with bytes, or an LzmaError INSTANCE, per entry; only
+        what concerns the whole call is raised"""
+        wants, total = self.layout(which)
+        out = ctypes.create_string_buffer(max(total, 1))
+        res = self._extract("xlz_7z_extract", ctx, wants, ctypes.cast(out, ctypes.c_void_p), total, verify)
+        base = ctypes.addressof(out)
+        return [ctypes.string_at(base + w[1], n) if st == OK else LzmaError(st, "xlz_7z_extract: entry %d" % w[0])
+                for w, (st, n, _) in zip(wants, res)]
+
+    def read(self, ctx, which, verify=True):
+        """one entry's bytes (b"" for an entry without a stream); raises LzmaError"""
+        got = self.extract(ctx, [self.index(which)], verify=verify)[0]
+        if isinstance(got, LzmaError):
+            raise got
+        return got
+
+    def extract_tensor(self, ctx, which, verify=True, align=1, out=None):
+        """extract_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least the
+        layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(entry, off, out_len, status)]): an entry is
+        tensor[off:off + out_len] where its status is OK"""
+        import torch  # (only here: importing lzma_amd does not import torch)
+        dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
+        wants, total = self.layout(which, align)
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
+        elif out.numel() < total:
+            raise LzmaError(ERR_OUT_CAP, "the layout needs %d bytes, out holds %d" % (total, out.numel()))
+        torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
+        res = self.extract_device(ctx, wants, out.data_ptr(), out.numel(), verify=verify)
+        return out, [(w[0], w[1], n, st) for w, (st, n, _) in zip(wants, res)]
+
+    def close(self):
+        if self._h:
+            N.lib().xlz_7z_close(self._h)
             self._h = ctypes.c_void_p()
         if getattr(self, "_held", False):
             self._held = False

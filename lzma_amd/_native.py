@@ -61,6 +61,8 @@ EXPORTS = [
     "xlz_xz_open", "xlz_xz_close", "xlz_xz_file_info", "xlz_xz_file_blocks", "xlz_xz_cover", "xlz_xz_read", "xlz_xz_read_device",
     "xlz_ctx_last_xz_read_stats",
     "xlz_xz_many_layout", "xlz_xz_decode_many", "xlz_xz_decode_many_device", "xlz_ctx_last_xz_many_stats",
+    "xlz_7z_open", "xlz_7z_close", "xlz_7z_archive_info", "xlz_7z_archive_entries", "xlz_7z_archive_folders", "xlz_7z_cover",
+    "xlz_7z_extract_layout", "xlz_7z_extract", "xlz_7z_extract_device", "xlz_ctx_last_7z_extract_stats",
 ]
 
 
@@ -202,6 +204,34 @@ class XzManyResult(ctypes.Structure):
 class XzManyStats(ctypes.Structure):
     _fields_ = [("files", ctypes.c_uint64), ("failed_files", ctypes.c_uint64), ("blocks", ctypes.c_uint64),
                 ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64)]
+
+
+SZ_NO_FOLDER = 0xFFFFFFFFFFFFFFFF
+SZ_ENTRY_HAS_STREAM, SZ_ENTRY_HAS_CRC, SZ_ENTRY_IS_DIR, SZ_ENTRY_IS_ANTI, SZ_ENTRY_HAS_MTIME, SZ_ENTRY_HAS_ATTRIBUTES = 1, 2, 4, 8, 16, 32
+
+
+class SzEntry(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint64), ("folder", ctypes.c_uint64), ("folder_off", ctypes.c_uint64), ("substream", ctypes.c_uint64),
+                ("mtime", ctypes.c_uint64), ("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint32), ("crc", ctypes.c_uint32),
+                ("attributes", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class SzWant(ctypes.Structure):
+    _fields_ = [("entry", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64)]
+
+
+class SzFileResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("unverified", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
+
+
+class SzCoverItem(ctypes.Structure):
+    _fields_ = [("folder", ctypes.c_uint64), ("decode_len", ctypes.c_uint64), ("in_len", ctypes.c_uint64)]
+
+
+class SzExtractStats(ctypes.Structure):
+    _fields_ = [("entries", ctypes.c_uint64), ("empty_entries", ctypes.c_uint64), ("failed_entries", ctypes.c_uint64),
+                ("folders", ctypes.c_uint64), ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64),
+                ("folder_bytes", ctypes.c_uint64), ("copied_bytes", ctypes.c_uint64)]
 
 
 class Lzma2Unit(ctypes.Structure):
@@ -410,6 +440,18 @@ def lib():
         L.xlz_xz_decode_many.argtypes = [vp, ctypes.POINTER(XzManyFile), sz, vp, sz, i32, ctypes.POINTER(XzManyResult)]
         L.xlz_xz_decode_many_device.argtypes = L.xlz_xz_decode_many.argtypes
         L.xlz_ctx_last_xz_many_stats.argtypes = [vp, ctypes.POINTER(XzManyStats)]
+    if hasattr(L, "xlz_7z_open"):  # (an older library loaded through XLZ_SO has no file table)
+        L.xlz_7z_open.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+        L.xlz_7z_close.argtypes = [vp]
+        L.xlz_7z_close.restype = None
+        L.xlz_7z_archive_info.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_7z_archive_entries.argtypes = [vp, ctypes.POINTER(SzEntry), sz, vp, sz]
+        L.xlz_7z_archive_folders.argtypes = [vp, ctypes.POINTER(SzFolder), sz]
+        L.xlz_7z_cover.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(SzCoverItem), sz, ctypes.POINTER(sz)]
+        L.xlz_7z_extract_layout.argtypes = [vp, ctypes.POINTER(SzWant), sz, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_7z_extract.argtypes = [vp, vp, ctypes.POINTER(SzWant), sz, vp, sz, i32, ctypes.POINTER(SzFileResult)]
+        L.xlz_7z_extract_device.argtypes = L.xlz_7z_extract.argtypes
+        L.xlz_ctx_last_7z_extract_stats.argtypes = [vp, ctypes.POINTER(SzExtractStats)]
     _lib = L
     return L
 

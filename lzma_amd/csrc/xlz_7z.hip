@@ -12,15 +12,18 @@
 // coder that is LZMA, LZMA2 or Copy and one packed stream; in filter mode 1 lines of Delta / BCJ filters
 // behind one such coder; in bcj2 mode 1 / 2 the two BCJ2 forms (find_bcj2), whose four streams are merged
 // on the device (xlz_bcj2_dev.hip).  Other coder graphs, encryption and multi-volume archives are reported
-// per folder as unsupported.  File names and
-// attributes (FilesInfo) are not parsed: the output is the folders' bytes back to back, which is
-// the archive's files back to back.
+// per folder as unsupported.  The index and decode calls do not
+// look at file names and attributes (FilesInfo): their output is the folders' bytes back to back, which is
+// the archive's files back to back.  xlz_7z_open (at the end of this file) parses FilesInfo too -- xlz_7z_files.h -- and
+// keeps the table; xlz_7z_extract.hip extracts chosen files with it.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include "../../include/xlz.h"
+#include "xlz_7z_files.h"
 #include "xlz_check.h"
 #include "xlz_check_host.h"
 
@@ -33,51 +36,12 @@ enum : uint8_t {
 };
 
 const uint8_t kMagic[6] = {'7', 'z', 0xBC, 0xAF, 0x27, 0x1C};
-constexpr uint64_t kMaxItems = 1u << 24; // folders / streams / files we are willing to index
+using xlz7zf::kMaxItems; // folders / streams / files we are willing to index
 
 uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | (uint64_t)le32(p + 4) << 32; }
 
-// bounded reader over a header
-struct Rd {
-    const uint8_t *p;
-    size_t n, pos = 0;
-    bool bad = false;
-    size_t left() const { return n - pos; }
-    uint8_t byte()
-    {
-        if (pos >= n) {
-            bad = true;
-            return 0;
-        }
-        return p[pos++];
-    }
-    // 7z "NUMBER": the count of leading one bits of the first byte = extra bytes (little endian)
-    uint64_t number()
-    {
-        const uint8_t first = byte();
-        uint8_t mask = 0x80;
-        uint64_t v = 0;
-        for (int i = 0; i < 8; i++) {
-            if (!(first & mask)) {
-                v |= (uint64_t)(first & (mask - 1)) << (8 * i);
-                return v;
-            }
-            v |= (uint64_t)byte() << (8 * i);
-            mask >>= 1;
-        }
-        return v;
-    }
-    bool skip(uint64_t k)
-    {
-        if (k > n - pos) {
-            bad = true;
-            return false;
-        }
-        pos += (size_t)k;
-        return true;
-    }
-};
+using xlz7zf::Rd; // bounded reader over a header
 
 struct Digests {
     std::vector<uint8_t> defined;
@@ -753,7 +717,14 @@ int locate_header(const uint8_t *file, size_t len, const uint8_t *&hdr, size_t &
 
 // the archive's MAIN StreamsInfo.  An encoded header (what 7-Zip writes by default) is itself a
 // folder: it is decoded with the batch engine first (needs ctx).
-int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std::vector<uint8_t> &decoded_header, bool bcj2 = false)
+// rest (optional, xlz_7z_open): what follows the StreamsInfo inside the header -- FilesInfo, if there is one; it points into
+// the file or into decoded_header
+struct HeaderRest {
+    const uint8_t *p = nullptr;
+    size_t n = 0;
+};
+int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std::vector<uint8_t> &decoded_header, bool bcj2 = false,
+                 HeaderRest *rest = nullptr)
 {
     const uint8_t *hdr;
     size_t hl;
@@ -795,7 +766,12 @@ int main_streams(xlz_ctx *ctx, const uint8_t *file, size_t len, Streams &s, std:
             t = r.byte();
         }
         if (t == kAdditionalStreamsInfo) return XLZ_ERR_UNSUPPORTED;
-        if (t == kMainStreamsInfo) return read_streams_info(r, s, bcj2);
+        if (t == kMainStreamsInfo) {
+            st = read_streams_info(r, s, bcj2);
+            if (st == XLZ_OK && rest) rest->p = r.p + r.pos, rest->n = r.left();
+            return st;
+        }
+        if (!r.bad && rest) rest->p = r.p + r.pos - 1, rest->n = r.left() + 1; // (from the byte that was no StreamsInfo)
         return r.bad ? XLZ_ERR_RESULT : XLZ_OK; // no streams: only empty files
     }
     return XLZ_ERR_UNSUPPORTED;
@@ -996,4 +972,76 @@ static int sz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     if (st != XLZ_OK) return st;
     *out_len = total;
     return XLZ_OK;
+}
+
+// ---------------------------------------------------------------- the file table ----
+// xlz_7z_index_bcj2's parse, then FilesInfo (xlz_7z_files.h).  What uses the table on the device is in xlz_7z_extract.hip.
+extern "C" int xlz_7z_open(xlz_ctx *ctx, const uint8_t *file, size_t len, xlz_7z_archive **a)
+{
+    if (!a) return XLZ_ERR_BAD_ARG;
+    *a = nullptr;
+    if (!file) return XLZ_ERR_BAD_ARG;
+    Streams s;
+    std::vector<uint8_t> dh;
+    HeaderRest rest;
+    int st = main_streams(ctx, file, len, s, dh, true, &rest);
+    if (st != XLZ_OK) return st;
+    xlz_7z_archive *h = new (std::nothrow) xlz_7z_archive;
+    if (!h) return XLZ_ERR_DEVICE;
+    h->file = file, h->len = len;
+    std::vector<xlz_7z_bcj2> recs;
+    st = place_folders(s, len, h->folders, true, &recs);
+    xlz7zf::Files files;
+    if (st == XLZ_OK && rest.n && rest.p[0] == kFilesInfo) {
+        size_t used = 0;
+        st = xlz7zf::parse_files(rest.p + 1, rest.n - 1, files, &used);
+        // (behind the section: the header's end mark)
+        if (st == XLZ_OK && !(rest.n - 1 - used >= 1 && rest.p[1 + used] == kEnd)) st = XLZ_ERR_RESULT;
+    } else if (st == XLZ_OK && rest.n && rest.p[0] != kEnd) {
+        st = XLZ_ERR_RESULT;
+    }
+    if (st == XLZ_OK) st = xlz7zf::build_entries(files, h->folders.data(), h->folders.size(), s.subs.data(), s.subs.size(), h->entries);
+    if (st != XLZ_OK) {
+        delete h;
+        return st;
+    }
+    h->subs.swap(s.subs), h->names.swap(files.names);
+    for (size_t i = 0; i < h->folders.size(); i++)
+        if (s.folders[i].chain)
+            for (const auto &stp : s.folders[i].steps) {
+                xlz_filter_step q;
+                memset(&q, 0, sizeof q);
+                q.stream = i, q.id = stp.first, q.param = stp.second;
+                h->steps.push_back(q);
+            }
+    for (const xlz_7z_entry &e : h->entries) h->total_size += e.size; // (no wrap: the folders' sizes add up, place_folders)
+    *a = h;
+    return XLZ_OK;
+}
+
+extern "C" void xlz_7z_close(xlz_7z_archive *a) { delete a; }
+
+extern "C" int xlz_7z_archive_info(const xlz_7z_archive *a, size_t *n_entries, size_t *n_folders, size_t *name_bytes, uint64_t *total_size)
+{
+    if (!a) return XLZ_ERR_BAD_ARG;
+    if (n_entries) *n_entries = a->entries.size();
+    if (n_folders) *n_folders = a->folders.size();
+    if (name_bytes) *name_bytes = a->names.size();
+    if (total_size) *total_size = a->total_size;
+    return XLZ_OK;
+}
+
+extern "C" int xlz_7z_archive_entries(const xlz_7z_archive *a, xlz_7z_entry *entries, size_t max_entries, char *names, size_t names_cap)
+{
+    if (!a || (!entries && max_entries) || (!names && names_cap)) return XLZ_ERR_BAD_ARG;
+    std::copy_n(a->entries.begin(), std::min(max_entries, a->entries.size()), entries);
+    std::copy_n(a->names.begin(), std::min(names_cap, a->names.size()), names);
+    return a->entries.size() > max_entries || a->names.size() > names_cap ? XLZ_ERR_OUT_CAP : XLZ_OK;
+}
+
+extern "C" int xlz_7z_archive_folders(const xlz_7z_archive *a, xlz_7z_folder *folders, size_t max_folders)
+{
+    if (!a || (!folders && max_folders)) return XLZ_ERR_BAD_ARG;
+    std::copy_n(a->folders.begin(), std::min(max_folders, a->folders.size()), folders);
+    return a->folders.size() > max_folders ? XLZ_ERR_OUT_CAP : XLZ_OK;
 }

@@ -16,6 +16,8 @@ void xlz_internal_pack_stats_reset(xlz_ctx *ctx);
 void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s);
 // what xlz_ctx_last_xz_many_stats reports: set by every xlz_xz_decode_many / xlz_xz_decode_many_device that ran
 void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s);
+// what xlz_ctx_last_7z_extract_stats reports: set by every xlz_7z_extract / xlz_7z_extract_device that ran
+void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s);
 // xlz_decode_batch with what `post` asks for behind it: xlz_decode_batch_checked, _filtered and _digests are this
 int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post);
 
@@ -49,8 +51,13 @@ struct DeviceDest {
     // tolerant (xlz_xz_decode_many_device: ONE batch over the blocks of many files): a stream that failed, or that did not
     // produce want_out[i] / use want_in[i], does not end the call.  It is left out of post.steps, of post.ranges (whose
     // outputs stay as the caller set them) and of the pack; the caller reads results[] and folds them into its files.
-    // Not with items, no_pack or bcj2.
+    // With items: every item of such a stream is left out.  Not with no_pack or bcj2.
     bool tolerant = false;
+    // what a stream must end in (tolerant only, xlz_7z_extract: folders that are cut on purpose).  Absent, or XLZ_OK for
+    // stream i: as above -- any status >= 0.  A negative want_status[i]: exactly that status, with want_out[i] bytes
+    // and, where want_in is given and want_in[i] is not kAnyInput, want_in[i] bytes of input used.
+    const int32_t *want_status = nullptr;
+    static constexpr uint64_t kAnyInput = ~(uint64_t)0;
 };
 // a device block of at least `bytes` from the context's pool (xlz_7z_decode with a BCJ2 folder decodes into one), its
 // download into host memory once the context's stream has drained, and its return

@@ -34,6 +34,7 @@
 #include "xlz_filter_dev.h"
 #include "xlz_pack_dev.h"
 #include "xlz_bcj2_dev.h"
+#include "xlz_7z_files.h"
 #include "xlz_xz_many.h"
 
 using namespace xlz;
@@ -255,6 +256,7 @@ struct xlz_ctx {
     xlz_pack_stats last_pack = {}; // xlz_ctx_last_pack_stats (xlz_pack_dev.hip)
     xlz_xz_read_stats last_xz_read = {}; // xlz_ctx_last_xz_read_stats (xlz_xz.hip)
     xlz_xz_many_stats last_xz_many = {}; // xlz_ctx_last_xz_many_stats (xlz_xz.hip)
+    xlz_7z_extract_stats last_7z_extract = {}; // xlz_ctx_last_7z_extract_stats (xlz_7z_extract.hip)
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
     xlz_bcj2_stats last_bcj2 = {};
@@ -2426,6 +2428,13 @@ void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s)
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->last_xz_many = s;
 }
+// chosen files of a .7z archive (xlz_7z_extract.hip: xlz_7z_extract / xlz_7z_extract_device)
+extern "C" int xlz_ctx_last_7z_extract_stats(xlz_ctx *ctx, xlz_7z_extract_stats *out) { return last_stats(ctx, &xlz_ctx::last_7z_extract, out); }
+void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_7z_extract = s;
+}
 
 // ---------------------------------------------------------------- BCJ2 folders ----
 namespace xlz {
@@ -3455,12 +3464,14 @@ int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size
 // batch on the context's stream, and behind it a line of stages that each publish what they did: the filters, the
 // digests of the ranges over streams, the pack, the BCJ2 merges, the digests of the ranges over the destination, the copies.
 static_assert(xlzmany::kMaxDeviceBlock == kMaxUnitBytes, "xlz_xz_many.h: which blocks the device form refuses before its batch");
+static_assert(xlz7zf::kMaxDeviceFolder == kMaxUnitBytes, "xlz_7z_files.h: which folders an extraction refuses before its batch");
 int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post,
                                const DeviceDest &dest)
 {
     if (!ctx || (!streams && n) || (!results && n) || (n && (!dest.want_out || (!dest.dst_off && !dest.have_items)))) return XLZ_ERR_BAD_ARG;
     if (dest.have_items && ((!dest.items && dest.n_items) || dest.no_pack)) return XLZ_ERR_BAD_ARG;
-    if (dest.tolerant && (dest.have_items || dest.no_pack || dest.n_bcj2)) return XLZ_ERR_BAD_ARG;
+    if (dest.tolerant && (dest.no_pack || dest.n_bcj2)) return XLZ_ERR_BAD_ARG;
+    if (dest.want_status && !dest.tolerant) return XLZ_ERR_BAD_ARG;
     if (post_args(post, streams, n, true) != XLZ_OK) return XLZ_ERR_BAD_ARG;
     std::vector<size_t> of_streams, of_dest; // post.ranges by where their bytes lie
     for (size_t q = 0; q < post.n_ranges; q++) {
@@ -3504,7 +3515,11 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         if (st == XLZ_OK) st = xlz_batch_run(b);
         if (st == XLZ_OK) st = xlz_batch_results(b, results);
         auto as_announced = [&](size_t i) {
-            return results[i].status >= 0 && results[i].out_len == dest.want_out[i] && (!dest.want_in || results[i].in_consumed == dest.want_in[i]);
+            const bool any_in = !dest.want_in || (dest.want_status && dest.want_in[i] == DeviceDest::kAnyInput);
+            if (dest.want_status && dest.want_status[i] < 0) // (a stream that is cut on purpose: that one outcome)
+                return results[i].status == dest.want_status[i] && results[i].out_len == dest.want_out[i] &&
+                       (any_in || results[i].in_consumed == dest.want_in[i]);
+            return results[i].status >= 0 && results[i].out_len == dest.want_out[i] && (any_in || results[i].in_consumed == dest.want_in[i]);
         };
         for (size_t i = 0; i < n && st == XLZ_OK && !dest.tolerant; i++) // the first stream that failed, or that is not what its container says
             if (results[i].status < 0)
