@@ -18,7 +18,7 @@ from pipeline_streams import Want, alone_job, flat_call, mismatches, raw2_job  #
 import corpus  # noqa: E402
 import lzma_amd  # noqa: E402
 import lzma_craft  # noqa: E402
-from lzma_amd import FMT_LZMA2_RAW, FMT_LZMA_ALONE  # noqa: E402
+from lzma_amd import FMT_LZMA2_RAW, FMT_LZMA_ALONE, Stream  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -51,6 +51,15 @@ def kernel_of(ctx, streams):
         return b.kernel_name(), b.launch_info()
     finally:
         b.close()
+
+
+def cus(ctx):
+    """CUs of the device, read off a launch of many rounds: 65 536 tiny default-parameter streams are more than 3.2 rounds
+    of 24 per CU on anything up to 850 CUs, and such a launch has 24 workgroups per CU"""
+    tiny = Stream(corpus.compress_alone(b"x"), FMT_LZMA_ALONE, out_cap=1)
+    name, (workgroups, _) = kernel_of(ctx, [tiny] * 65536)
+    assert name == KERNEL_NAMES["branchy"] and workgroups % BRANCHY_PER_CU == 0, (name, workgroups)
+    return workgroups // BRANCHY_PER_CU
 
 
 # ------------------------------------------------------------------ what the host's scan sees of a stream ----

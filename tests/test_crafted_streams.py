@@ -353,6 +353,85 @@ def test_long_first_epoch_and_large_model_streams_cpu():
     assert max(seen) == 12 and {5, 6, 7, 8}.intersection(seen) and min(seen) <= 4
 
 
+def test_hbm_corpora_meet_only_the_hbm_kernel_cpu(monkeypatch):
+    """The conditions under which tests/test_gpu_hbm_kernel.py means something (tests/hbm_streams.py): every stream of
+    both corpora announces lc + lp > 8 to the host's scan and has no unit in the LDS-model launch -- but for the LZMA1
+    streams cut inside their header, which the host settles, by name --; the crafter's own window model of every valid
+    stream is the oracle's output with status 0; the oracle's statuses over the edge corpus spread over every kind of
+    end; the stale-read streams do read behind a reset; the re-run corpus is larger than the re-runs' grids.  No
+    stream is left out of a comparison."""
+    import collections
+    import hbm_streams as hs
+    import kernel_streams as ks
+    import lzma_amd
+    import lzma_craft
+    import lzma_pydec
+    assert {lc + lp for lc, lp, _ in hs.BIG_PROPS} == {9, 10, 11, 12} and {pb for _, _, pb in hs.BIG_PROPS} == {0, 1, 2, 3, 4}
+    edge = hs.hbm_edge_entries()
+    many = hs.hbm_many_entries(2 * 256 + 37)
+    assert [e[1] for e in edge] == hs.hbm_edge_jobs() and len({e[0] for e in edge}) == len(edge) > 1300
+    seen = collections.Counter()
+    checked = settled = valid = units = 0
+    for corpus_name, entries in (("edge", edge), ("many", many)):
+        for name, (s, want), crafted in entries:
+            out, status, consumed = want()
+            if corpus_name == "edge":
+                seen[status] += 1
+            assert ks.lds_units(s) == 0, name
+            if name in hs.HOST_SETTLED:
+                assert corpus_name == "edge" and s.fmt == lzma_amd.FMT_LZMA_ALONE and len(s.data) < 13 and status == oracle.ERR_HEADER_EOF, name
+                settled += 1
+            else:
+                assert hs.announces_a_big_model(s), name
+                units += 1 if s.fmt == lzma_amd.FMT_LZMA_ALONE else len(lzma_amd.lzma2_units(s.data))
+            if crafted is not None:
+                assert (out, status) == (crafted, 0), name
+                valid += 1
+            checked += 1
+    assert checked == len(edge) + len(many) and settled == len(hs.HOST_SETTLED) == 26
+    assert valid >= 16 + 12 + 40 + 40 + len(many) // 3
+    for status in (oracle.OK, oracle.OK_INPUT_EOF, oracle.ERR_RESULT, oracle.ERR_HEADER_EOF, oracle.ERR_UNEXPECTED_EOF,
+                   oracle.ERR_OUT_CAP):
+        assert seen[status] >= 5, (status, dict(seen))
+    # the tiny units: as many as asked for, lc + lp = 12 in front of smaller models, every kind
+    assert sum(2 if "two units" in e[0] else 1 for e in many) == 2 * 256 + 37
+    assert sum(2 if "two units" in e[0] else 1 for e in hs.hbm_many_entries(300)) == 300
+    big = [i for i, e in enumerate(many) if max(lc + lp for lc, lp, _ in ks.visible_props(e[1][0])) == 12]
+    assert 25 <= len(big) <= 40 and all(any(k in e[0] for e in many) for k in hs.MANY_KINDS)
+    assert all(300 <= len(e[2]) <= 3000 + 3 * 272 for e in many if e[2] is not None)   # (a chunk's last copy may overshoot)
+    # the multi-unit streams, whole and damaged, are several units to the host's scan
+    for part in hs.multi_unit_entries():
+        assert all(len(lzma_amd.lzma2_units(e[1][0].data)) > 1 for e in part)
+    # the short cuts of the LZMA2 stream are what the edge corpus leaves to the LDS-model launch
+    assert [ks.lds_units(j[0]) for j in hs.short_cut_jobs()] == [1] * hs.LZMA2_FIRST_PROPS_AT
+    # the re-runs: more streams than the widest re-run's 32 workgroups; the walking streams show lc + lp = 9 and hide more
+    walks, stale = hs.walk_entries(), hs.stale_read_entries()
+    assert len(walks) == len(stale) == 40
+    for name, (s, want), crafted in walks:
+        assert [lc + lp for lc, lp, _ in ks.visible_props(s)] == [9] and len(lzma_amd.lzma2_units(s.data)) == 1, name
+        assert lzma_pydec.lzma2_raw(s.data, s.dict_size)[:2] == (crafted, 0), name
+    # every stale-read stream reads behind a reset: a window that is cleared there gives other bytes
+
+    class ClearedWindow(lzma_craft.Window):
+        def reset(self):
+            super().reset()
+            self.buf = bytearray(self.size)
+    differ = 0
+    for name, (s, want), crafted in stale:
+        assert lzma_pydec.lzma2_raw(s.data, s.dict_size) == want(), name
+        with monkeypatch.context() as m:
+            m.setattr(lzma_pydec, "Window", ClearedWindow)
+            differ += lzma_pydec.lzma2_raw(s.data, s.dict_size)[0] != crafted
+    assert differ == len(stale), differ
+    # the damaged two-unit streams of the exact re-run: two units to the scan, the first one short of its header
+    redo = hs.hbm_redo_entries(256 + 37)
+    assert len(redo) == 256 + 37 and len({e[0] for e in redo}) == len(redo)
+    for name, (s, want), _ in redo:
+        u = lzma_amd.lzma2_units(s.data)
+        assert len(u) == 2 and hs.announces_a_big_model(s) and ks.lds_units(s) == 0, name
+        assert len(want()[0]) != u[0]["out_len"] + u[1]["out_len"] or want()[1] != 0, name
+
+
 @pytest.mark.gpu
 def test_random_crafted_lzma2_streams_gpu(ctx):
     import lzma_amd

@@ -20,6 +20,7 @@ import lzma_amd
 import lzma_craft
 import lzma_pydec
 import pipeline_streams as ps
+from kernel_streams import cus as _cus
 from lzma_amd import FMT_LZMA_ALONE, Stream
 
 pytestmark = pytest.mark.gpu
@@ -134,15 +135,6 @@ def _fillers():
         _FILLERS["v"] = corpus.make_alone_batch("M", 1024, 8192, base_seed=91_000,
                                                 preset={"mode": 1, "mf": 3, "nice_len": 32, "depth": 2})
     return _FILLERS["v"]
-
-
-def _cus(ctx):
-    """CUs of the device, read off a launch of many rounds: 65 536 tiny default-parameter streams are more than 3.2 rounds
-    of 24 per CU on anything up to 850 CUs, and such a launch has 24 workgroups per CU"""
-    tiny = Stream(corpus.compress_alone(b"x"), FMT_LZMA_ALONE, out_cap=1)
-    name, (workgroups, _) = ks.kernel_of(ctx, [tiny] * 65536)
-    assert name == ks.KERNEL_NAMES["branchy"] and workgroups % ks.BRANCHY_PER_CU == 0, (name, workgroups)
-    return workgroups // ks.BRANCHY_PER_CU
 
 
 def _edges_among_fillers(n_units):

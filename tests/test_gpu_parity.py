@@ -347,7 +347,7 @@ def test_units_of_one_stream_and_blocks_of_one_file_over_three_contexts(ctx):
         c.close()
 
 
-# ------------------------------------------------ models too large for LDS (lc+lp > 6) ----
+# ------------------------------------------------ models too large for LDS (lc+lp > 8) ----
 def test_large_lc_lp_models_live_in_hbm(ctx):
     """The reference accepts lc <= 8, lp <= 4 (reader1.go:210-221): up to 0x300 << 12 probs.
     liblzma refuses to ENCODE lc+lp > 4, so these streams are ordinary payloads relabelled with
