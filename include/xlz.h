@@ -999,6 +999,71 @@ typedef struct xlz_7z_extract_stats {
 } xlz_7z_extract_stats;
 int xlz_ctx_last_7z_extract_stats(xlz_ctx *ctx, xlz_7z_extract_stats *out);
 
+/* ---- the members of a .tar image, in host or device memory -----------------------------
+ * Outside the reference (which has no tar code).  Almost every .xz file is a tarball; decoded into device memory
+ * (xlz_xz_decode_device) it is one flat image, and where its members lie follows from a chain of headers, each of which
+ * says where the next one is.  xlz_tar_scan_device finds them without downloading the image and without one round trip per
+ * member: a kernel classifies every 512-byte block in HBM by its checksum field (lzma_amd/csrc/xlz_tar_dev.h: zero /
+ * header candidate / other), the flags (len / 512 bytes) and then the candidate blocks alone come to the host, the host
+ * walks the chain over them (lzma_amd/csrc/xlz_tar_walk.h), a second gather fetches the data of the meta entries the walk
+ * met (GNU long names, pax records), and the walk is finished.  Candidates that are file data -- a tar stored inside the
+ * tar -- are downloaded but never reached; if every block is a candidate the download equals the image: correct, slow,
+ * and visible in xlz_tar_stats.  The image is only read.  xlz_tar_parse_host is the same walk over a host image, no
+ * device needed; both give the same table, end_status and end_off for the same bytes.
+ *
+ * The table is what Python's tarfile.getmembers() reports: per member its name and link name (bytes AS STORED, each
+ * NUL-terminated in one pool: A CALLER THAT WRITES FILES MUST NOT TRUST A NAME AS A PATH), size, type ('0' for a regular
+ * file, '5' a directory, '1' / '2' hard and symbolic links, ...; a '\0' type is reported as it is, or as '5' when the
+ * name ends in '/'), mode, uid, gid, mtime, hdr_off (the offset of its header, or of the first GNU long-name / pax
+ * header in front of it: tarfile's offset) and data_off (offset_data).  On the device a member is bytes
+ * [data_off, data_off + size) of the image, 512-aligned: a view, no copy.  ustar, GNU ('L' / 'K' long names, base-256
+ * numbers) and pax ('x' / 'g' records: path, linkpath, size, mtime, uid, gid) archives are read; the rules are at the head
+ * of xlz_tar_walk.h.
+ *
+ * A call returns XLZ_OK whenever the walk ran; how the walk ENDED is end_status: XLZ_OK (a zero block, or the image's end
+ * at a header position); XLZ_ERR_UNEXPECTED_EOF (the image ends inside a header or inside a member's data);
+ * XLZ_ERR_RESULT (a block that is no header where one must be, a malformed number or pax record, meta data over 1 MiB);
+ * XLZ_ERR_UNSUPPORTED (old GNU sparse 'S', multi-volume 'M', GNU.sparse.* pax keys).  The members in front of that
+ * place stay in the table, end_off is the offset of the header where the walk stopped.
+ *
+ * XLZ_ERR_BAD_ARG: out is NULL; image is NULL with len > 0; ctx is NULL; d_image is not a multiple of 16 (device memory
+ * from hipMalloc and torch is) or not len bytes of device memory of the context's device.  len < 512 launches nothing.
+ * xlz_xz_tar_list: the whole of an open .xz file (xlz_xz_open) decoded into device scratch from the context's pool by
+ * xlz_xz_read_device for [0, size) -- the same checks, filters, statuses and *unverified as that call --, scanned, and
+ * the scratch given back: the listing of a .tar.xz.  Its members are then read with xlz_xz_read / xlz_xz_read_device over
+ * (data_off, size), which decode only the blocks that hold them.                                                   */
+typedef struct xlz_tar xlz_tar;
+typedef struct xlz_tar_entry { /* 72 bytes */
+    uint64_t hdr_off, data_off, size;
+    int64_t mtime_s;     /* whole seconds since 1970-01-01 UTC (floor)                                     */
+    uint32_t mtime_ns;   /* a pax mtime's fraction; 0 otherwise                                            */
+    uint32_t mode, uid, gid;
+    uint32_t name_off, name_len, link_off, link_len; /* into the name pool, lengths without the NUL        */
+    uint8_t type;
+    uint8_t reserved[7];
+} xlz_tar_entry;
+int xlz_tar_parse_host(const void *image, uint64_t len, xlz_tar **out);
+int xlz_tar_scan_device(xlz_ctx *ctx, const void *d_image, uint64_t len, xlz_tar **out);
+int xlz_xz_tar_list(xlz_ctx *ctx, const xlz_xz_file *f, int verify, xlz_tar **out, size_t *unverified);
+/* every pointer but `t` may be NULL */
+void xlz_tar_info(const xlz_tar *t, size_t *n_entries, size_t *name_bytes, int *end_status, uint64_t *end_off);
+/* at most cap entries and names_cap bytes of the pool are copied; XLZ_ERR_OUT_CAP: there are more of either */
+int xlz_tar_entries(const xlz_tar *t, xlz_tar_entry *e, size_t cap, void *names, size_t names_cap);
+void xlz_tar_close(xlz_tar *t);
+/* Of the most recent xlz_tar_scan_device / xlz_xz_tar_list on `ctx` whose scan ran.                        */
+typedef struct xlz_tar_stats {
+    uint64_t blocks;           /* complete 512-byte blocks of the image                                    */
+    uint64_t zero_blocks;      /* flag 2                                                                   */
+    uint64_t candidate_blocks; /* flag 1: gathered and downloaded                                          */
+    uint64_t header_blocks;    /* headers the walk reached (meta entries included)                         */
+    uint64_t meta_bytes;       /* data blocks of meta entries, gathered and downloaded                     */
+    uint64_t downloaded_bytes; /* flags + candidate blocks + meta blocks                                   */
+    double kernel_ms;          /* the classify and gather kernels by HIP events                            */
+    uint32_t launches;
+    uint32_t reserved;
+} xlz_tar_stats;
+int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *s);
+
 #ifdef __cplusplus
 }
 #endif

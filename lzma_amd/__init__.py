@@ -202,6 +202,15 @@ class Context:
             raise LzmaError(st, "xlz_ctx_last_7z_extract_stats")
         return {f: getattr(s, f) for f, _ in N.SzExtractStats._fields_}
 
+    def last_tar_stats(self):
+        """of the most recent tar_scan_device / TarXzFile.list on this context whose scan ran: blocks, zero_blocks,
+        candidate_blocks (downloaded), header_blocks (reached by the walk), meta_bytes, downloaded_bytes, kernel_ms, launches"""
+        s = N.TarStats()
+        st = N.lib().xlz_ctx_last_tar_stats(self._h, ctypes.byref(s))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_tar_stats")
+        return {f: getattr(s, f) for f, _ in N.TarStats._fields_ if f != "reserved"}
+
     def bcj2_mode(self):
         L = N.lib()
         if not hasattr(L, "xlz_ctx_bcj2_mode"):  # (an older library loaded through XLZ_SO: it refuses every BCJ2 folder)
@@ -1403,6 +1412,131 @@ class SevenZipFile:
             self.close()
         except Exception:
             pass
+
+
+# ---- the members of a .tar image (include/xlz.h: xlz_tar_parse_host / xlz_tar_scan_device / xlz_xz_tar_list) ----
+TarEntry = collections.namedtuple("TarEntry", "name linkname size type mode uid gid mtime hdr_off data_off")
+TarTable = collections.namedtuple("TarTable", "entries end_status end_off")
+
+
+def _tar_table(h):
+    """the table of an xlz_tar handle, which is closed -> TarTable.  Names are bytes in the archive: decoded as UTF-8 with
+    surrogateescape, as tarfile does.  type is one byte, as tarfile's; mtime an int, or a float for a pax time with a fraction."""
+    L = N.lib()
+    try:
+        n, nb, end, off = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int(), ctypes.c_uint64()
+        L.xlz_tar_info(h, ctypes.byref(n), ctypes.byref(nb), ctypes.byref(end), ctypes.byref(off))
+        ents = (N.TarEntry * max(n.value, 1))()
+        pool = ctypes.create_string_buffer(max(nb.value, 1))
+        st = L.xlz_tar_entries(h, ents, n.value, ctypes.cast(pool, ctypes.c_void_p), nb.value)
+        if st != OK:
+            raise LzmaError(st, "xlz_tar_entries")
+    finally:
+        L.xlz_tar_close(h)
+    raw = pool.raw
+    entries = []
+    for i in range(n.value):
+        x = ents[i]
+        entries.append(TarEntry(raw[x.name_off:x.name_off + x.name_len].decode("utf-8", "surrogateescape"),
+                                raw[x.link_off:x.link_off + x.link_len].decode("utf-8", "surrogateescape"), x.size, bytes([x.type]), x.mode,
+                                x.uid, x.gid, x.mtime_s + x.mtime_ns * 1e-9 if x.mtime_ns else x.mtime_s, x.hdr_off, x.data_off))
+    return TarTable(entries, end.value, off.value)
+
+
+def tar_parse(image):
+    """xlz_tar_parse_host: the members of a .tar image in host memory (bytes) -> TarTable(entries, end_status, end_off): what
+    tarfile.getmembers() reports, and how the walk along the headers ended (OK, or the status and the offset of the header
+    where it stopped; the members in front of it are listed).  Host only, no device needed."""
+    if not isinstance(image, bytes):
+        image = bytes(image)
+    h = ctypes.c_void_p()
+    st = N.lib().xlz_tar_parse_host(ctypes.cast(ctypes.c_char_p(image), ctypes.c_void_p), len(image), ctypes.byref(h))
+    if st != OK:
+        raise LzmaError(st, "xlz_tar_parse_host")
+    return _tar_table(h)
+
+
+def tar_scan_device(ctx, dptr, n):
+    """xlz_tar_scan_device: the same for `n` bytes of device memory at the address `dptr` (a multiple of 16, on the context's
+    device): the blocks are classified where they lie, only the flags, the header candidates and the data of long-name /
+    pax entries come to the host.  Member i is bytes [data_off, data_off + size) of the image."""
+    h = ctypes.c_void_p()
+    st = N.lib().xlz_tar_scan_device(ctx._h, ctypes.c_void_p(int(dptr)), int(n), ctypes.byref(h))
+    if st != OK:
+        raise LzmaError(st, "xlz_tar_scan_device")
+    return _tar_table(h)
+
+
+def xz_tar_tensor(ctx, data, verify=True):
+    """a .tar.xz into device memory and its member table: xz_decode_tensor, then tar_scan_device over the tensor ->
+    (image, entries, end_status); member i is the view image[e.data_off:e.data_off + e.size]"""
+    image = xz_decode_tensor(ctx, data, verify=verify)
+    table = tar_scan_device(ctx, image.data_ptr() if image.numel() else 0, image.numel())
+    return image, table.entries, table.end_status
+
+
+class TarXzFile:
+    """One .tar.xz: the index of the .xz file (XzFile; host only) and, after list(), its member table.  Members are read
+    through the range reader over (data_off, size), so a read decodes only the .xz blocks that hold the wanted members
+    -- ONE batch per call.  `data` as for XzFile (borrowed, held until close()).  A context manager; close() may be repeated."""
+
+    def __init__(self, data):
+        self.xz = XzFile(data)
+        self.entries = self.names = self.end_status = self.end_off = None
+
+    def list(self, ctx, verify=True, strict=True):
+        """xlz_xz_tar_list: the whole file decoded into device scratch and scanned there -> the entries; fills .entries,
+        .names, .end_status and .end_off.  Raises LzmaError as a read of the whole file does, and -- unless strict is
+        False -- when the archive does not end cleanly (.entries then holds the members in front of that place)."""
+        h, unverified = ctypes.c_void_p(), ctypes.c_size_t()
+        st = N.lib().xlz_xz_tar_list(ctx._h, self.xz._handle(), 1 if verify else 0, ctypes.byref(h), ctypes.byref(unverified))
+        if st != OK:
+            raise LzmaError(st, "xlz_xz_tar_list")
+        ctx.last_xz_unverified = unverified.value
+        self.entries, self.end_status, self.end_off = _tar_table(h)
+        self.names = [e.name for e in self.entries]
+        if strict and self.end_status != OK:
+            raise LzmaError(self.end_status, "xlz_xz_tar_list: the archive ends at offset %d" % self.end_off)
+        return self.entries
+
+    def index(self, which):
+        """a member's index from an index or a name (the LAST member of that name, as tarfile.getmember)"""
+        if self.entries is None:
+            raise ValueError("TarXzFile.list() has not run")
+        if isinstance(which, str):
+            for i in range(len(self.names) - 1, -1, -1):
+                if self.names[i] == which:
+                    return i
+            raise KeyError(which)
+        return range(len(self.entries))[int(which)]
+
+    def span(self, which):
+        """(data_off, n) of a member (index or name): where its bytes lie in the decoded file.  n is 0 for a member without
+        data (types '1'-'6': links, directories, devices), whatever its size field says."""
+        e = self.entries[self.index(which)]
+        return e.data_off, 0 if b"1" <= e.type <= b"6" else e.size
+
+    def read_many(self, ctx, which, verify=True):
+        """the bytes of the wanted members (indices or names) -> list[bytes]: ONE batch of the covering .xz blocks
+        (ctx.last_xz_read_stats())"""
+        return self.xz.read_ranges(ctx, [self.span(w) for w in which], verify=verify)
+
+    def read(self, ctx, which, verify=True):
+        return self.read_many(ctx, [which], verify=verify)[0]
+
+    def read_tensor(self, ctx, which, verify=True, out=None):
+        """one member into a torch.uint8 tensor on the context's device, as XzFile.read_tensor"""
+        off, n = self.span(which)
+        return self.xz.read_tensor(ctx, off, n, verify=verify, out=out)
+
+    def close(self):
+        self.xz.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---- many .xz files as one batch (include/xlz.h: xlz_xz_many_layout / xlz_xz_decode_many / xlz_xz_decode_many_device) ----

@@ -63,6 +63,8 @@ EXPORTS = [
     "xlz_xz_many_layout", "xlz_xz_decode_many", "xlz_xz_decode_many_device", "xlz_ctx_last_xz_many_stats",
     "xlz_7z_open", "xlz_7z_close", "xlz_7z_archive_info", "xlz_7z_archive_entries", "xlz_7z_archive_folders", "xlz_7z_cover",
     "xlz_7z_extract_layout", "xlz_7z_extract", "xlz_7z_extract_device", "xlz_ctx_last_7z_extract_stats",
+    "xlz_tar_parse_host", "xlz_tar_scan_device", "xlz_xz_tar_list", "xlz_tar_info", "xlz_tar_entries", "xlz_tar_close",
+    "xlz_ctx_last_tar_stats",
 ]
 
 
@@ -232,6 +234,19 @@ class SzExtractStats(ctypes.Structure):
     _fields_ = [("entries", ctypes.c_uint64), ("empty_entries", ctypes.c_uint64), ("failed_entries", ctypes.c_uint64),
                 ("folders", ctypes.c_uint64), ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64),
                 ("folder_bytes", ctypes.c_uint64), ("copied_bytes", ctypes.c_uint64)]
+
+
+class TarEntry(ctypes.Structure):
+    _fields_ = [("hdr_off", ctypes.c_uint64), ("data_off", ctypes.c_uint64), ("size", ctypes.c_uint64), ("mtime_s", ctypes.c_int64),
+                ("mtime_ns", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("uid", ctypes.c_uint32), ("gid", ctypes.c_uint32),
+                ("name_off", ctypes.c_uint32), ("name_len", ctypes.c_uint32), ("link_off", ctypes.c_uint32), ("link_len", ctypes.c_uint32),
+                ("type", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 7)]
+
+
+class TarStats(ctypes.Structure):
+    _fields_ = [("blocks", ctypes.c_uint64), ("zero_blocks", ctypes.c_uint64), ("candidate_blocks", ctypes.c_uint64),
+                ("header_blocks", ctypes.c_uint64), ("meta_bytes", ctypes.c_uint64), ("downloaded_bytes", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class Lzma2Unit(ctypes.Structure):
@@ -452,6 +467,17 @@ def lib():
         L.xlz_7z_extract.argtypes = [vp, vp, ctypes.POINTER(SzWant), sz, vp, sz, i32, ctypes.POINTER(SzFileResult)]
         L.xlz_7z_extract_device.argtypes = L.xlz_7z_extract.argtypes
         L.xlz_ctx_last_7z_extract_stats.argtypes = [vp, ctypes.POINTER(SzExtractStats)]
+    if hasattr(L, "xlz_tar_parse_host"):  # (an older library loaded through XLZ_SO lists no .tar members)
+        L.xlz_tar_parse_host.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.xlz_tar_scan_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)]
+        L.xlz_xz_tar_list.argtypes = [vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+        L.xlz_tar_info.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_tar_info.restype = None
+        L.xlz_tar_entries.argtypes = [vp, ctypes.POINTER(TarEntry), sz, vp, sz]
+        L.xlz_tar_close.argtypes = [vp]
+        L.xlz_tar_close.restype = None
+        L.xlz_ctx_last_tar_stats.argtypes = [vp, ctypes.POINTER(TarStats)]
+        L.xlz_internal_tar_classify_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.POINTER(ctypes.c_double)]
     _lib = L
     return L
 

@@ -18,6 +18,12 @@ void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s);
 void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s);
 // what xlz_ctx_last_7z_extract_stats reports: set by every xlz_7z_extract / xlz_7z_extract_device that ran
 void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s);
+// the device steps of xlz_tar_scan_device (xlz_tar_dev.hip) on the context's stream: the flags of the image's complete
+// 512-byte blocks -> flags_out, and blocks idx[0 .. n) dense -> out_host; *ms = the kernel's time.  What
+// xlz_ctx_last_tar_stats reports is set by every scan that ran.
+extern "C" int xlz_internal_tar_classify_device(xlz_ctx *ctx, const void *d_image, uint64_t len, uint8_t *flags_out, double *ms);
+int xlz_internal_tar_gather_device(xlz_ctx *ctx, const void *d_image, uint64_t len, const uint64_t *idx, size_t n, uint8_t *out_host, double *ms);
+void xlz_internal_tar_stats_set(xlz_ctx *ctx, const xlz_tar_stats &s);
 // xlz_decode_batch with what `post` asks for behind it: xlz_decode_batch_checked, _filtered and _digests are this
 int xlz_internal_decode_batch(xlz_ctx *ctx, const xlz_stream_desc *streams, size_t n, xlz_result *results, const PostWork &post);
 

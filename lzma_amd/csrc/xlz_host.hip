@@ -257,6 +257,7 @@ struct xlz_ctx {
     xlz_xz_read_stats last_xz_read = {}; // xlz_ctx_last_xz_read_stats (xlz_xz.hip)
     xlz_xz_many_stats last_xz_many = {}; // xlz_ctx_last_xz_many_stats (xlz_xz.hip)
     xlz_7z_extract_stats last_7z_extract = {}; // xlz_ctx_last_7z_extract_stats (xlz_7z_extract.hip)
+    xlz_tar_stats last_tar = {}; // xlz_ctx_last_tar_stats (xlz_tar_dev.hip)
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
     xlz_bcj2_stats last_bcj2 = {};
@@ -2434,6 +2435,99 @@ void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats 
 {
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->last_7z_extract = s;
+}
+
+// ---------------------------------------------------------------- .tar members of an image in device memory ----
+// The two device steps of xlz_tar_scan_device (xlz_tar_dev.hip), on the context's stream with scratch from its pool; each
+// waits for its kernel and its download.
+namespace xlz {
+int tar_classify_launch(const uint8_t *image, uint64_t len, uint8_t *flags, int num_cus, hipStream_t stream);
+int tar_gather_launch(const uint8_t *image, uint64_t len, const uint64_t *idx, uint64_t n, uint8_t *staging, int num_cus, hipStream_t stream);
+}
+namespace {
+struct TarScratch { // pool blocks and the two events of one step; the stream has drained before a block goes back
+    xlz_ctx *ctx;
+    void *blk[2] = {};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    explicit TarScratch(xlz_ctx *c) : ctx(c) {}
+    ~TarScratch()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : blk) ctx->pool.give(p);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    // queue() between the events, then `bytes` from src to the host's dst, a wait, the kernel's time
+    template <class Queue> int run(const char *what, Queue queue, void *dst, const void *src, size_t bytes, double *ms)
+    {
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, ctx->stream));
+        if (!queue()) {
+            if (getenv("XLZ_DEBUG")) fprintf(stderr, "xlz: launching the %s failed\n", what);
+            return XLZ_ERR_DEVICE;
+        }
+        HIP_TRY(hipEventRecord(ev1, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        float t = 0;
+        HIP_TRY(hipEventElapsedTime(&t, ev0, ev1));
+        *ms = t;
+        return XLZ_OK;
+    }
+};
+} // namespace
+// The flags of the len / 512 complete blocks of the image at d_image (a multiple of 16, len bytes of device memory of the
+// context's device) -> flags_out (host), the kernel's time by HIP events -> *ms.  Not part of the C ABI, but exported:
+// the tests and tools/tar_bench.py run the kernel alone through it.
+extern "C" int xlz_internal_tar_classify_device(xlz_ctx *ctx, const void *d_image, uint64_t len, uint8_t *flags_out, double *ms)
+{
+    if (!ctx || !ms || ((uintptr_t)d_image & 15)) return XLZ_ERR_BAD_ARG;
+    *ms = 0;
+    const uint64_t n_blocks = len >> 9;
+    if (!n_blocks) return XLZ_OK;
+    if (!d_image || !flags_out) return XLZ_ERR_BAD_ARG;
+    const int ok = device_dst_ok(ctx, d_image, (size_t)len);
+    if (ok != XLZ_OK) return ok;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    TarScratch s(ctx);
+    uint8_t *d_flags = static_cast<uint8_t *>(s.blk[0] = ctx->pool.take((size_t)n_blocks, false));
+    if (!d_flags) return XLZ_ERR_DEVICE;
+    return s.run(
+        "tar classify kernel",
+        [&] { return xlz::tar_classify_launch(static_cast<const uint8_t *>(d_image), len, d_flags, ctx->num_cus, ctx->stream) == 0; }, flags_out,
+        d_flags, (size_t)n_blocks, ms);
+}
+// Blocks idx[0 .. n) of the same image, dense -> out_host (512 * n bytes).  XLZ_ERR_BAD_ARG: an index outside the image's
+// complete blocks (nothing is launched then).
+int xlz_internal_tar_gather_device(xlz_ctx *ctx, const void *d_image, uint64_t len, const uint64_t *idx, size_t n, uint8_t *out_host, double *ms)
+{
+    if (!ctx || !ms || ((uintptr_t)d_image & 15)) return XLZ_ERR_BAD_ARG;
+    *ms = 0;
+    if (!n) return XLZ_OK;
+    if (!d_image || !idx || !out_host || n > (~(size_t)0 >> 10)) return XLZ_ERR_BAD_ARG;
+    for (size_t k = 0; k < n; k++)
+        if (idx[k] >= (len >> 9)) return XLZ_ERR_BAD_ARG;
+    const int ok = device_dst_ok(ctx, d_image, (size_t)len);
+    if (ok != XLZ_OK) return ok;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    TarScratch s(ctx);
+    uint64_t *d_idx = static_cast<uint64_t *>(s.blk[0] = ctx->pool.take(n * sizeof(uint64_t), false));
+    uint8_t *d_stage = static_cast<uint8_t *>(s.blk[1] = ctx->pool.take(n * 512, false));
+    if (!d_idx || !d_stage) return XLZ_ERR_DEVICE;
+    HIP_TRY(hipMemcpyAsync(d_idx, idx, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    return s.run(
+        "tar gather kernel",
+        [&] { return xlz::tar_gather_launch(static_cast<const uint8_t *>(d_image), len, d_idx, n, d_stage, ctx->num_cus, ctx->stream) == 0; },
+        out_host, d_stage, n * 512, ms);
+}
+extern "C" int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *out) { return last_stats(ctx, &xlz_ctx::last_tar, out); }
+void xlz_internal_tar_stats_set(xlz_ctx *ctx, const xlz_tar_stats &s)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_tar = s;
 }
 
 // ---------------------------------------------------------------- BCJ2 folders ----
