@@ -2,7 +2,9 @@
 Batch.filter on a device-resident batch, decode_batch_filtered in the three forms of the host pipeline, and the .xz / .7z
 front-ends in filter mode 1.  Everything is bit-exact.  The judge is liblzma (tests/filter_ref.py): for raw LZMA2 streams
 it decodes AND filters (filters=[..., LZMA2]); for the pipeline's stream sets, whose unfiltered results the oracle gives,
-the expected bytes are those results passed through filter_host, which tests/test_filter_dev.py holds against liblzma."""
+the expected bytes are those results passed through filter_host, which tests/test_filter_dev.py holds against liblzma.
+Content placed ON the seams of the kernels' work split (lane, wave, tile, window, chunk and group edges) is in
+tests/test_gpu_filter_edges.py; the buffers here meet those seams by chance."""
 import ctypes
 import lzma
 import random
