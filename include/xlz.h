@@ -1064,6 +1064,140 @@ typedef struct xlz_tar_stats {
 } xlz_tar_stats;
 int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *s);
 
+/* ---- the entries of a .zip archive: the table, and chosen entries as ONE batch -----------
+ * Outside the reference (which has no ZIP code; Go callers register it with archive/zip for method 14 and are then
+ * called once per entry).  Every entry of a ZIP archive is a stream of its own, so an archive written with method 14
+ * (LZMA: 7-Zip -tzip -mm=LZMA, WinZip .zipx, Python's zipfile.ZIP_LZMA) is thousands of independent LZMA1 streams, each
+ * with a known size and a CRC32: the shape the decoder is built for, with nothing to be found first.  Written from
+ * PKWARE's APPNOTE.TXT; the parser is lzma_amd/csrc/xlz_zip.h.
+ *
+ * xlz_zip_open (host only, no context) finds the end record -- the last PK\5\6 of the last 65 557 bytes at a position p
+ * with p + 22 + comment_len <= len, so bytes behind the comment are tolerated --, follows a ZIP64 locator 20 bytes in front
+ * of it to the ZIP64 end record (where the locator says, else right in front of the locator) and takes counts, size and
+ * offset from there; takes the central directory to end where that end record begins, so that
+ * shift = cd_pos_found - cd_offset_declared is the number of bytes in front of the archive (self-extractor stubs), added
+ * to every local header offset (an all-ones declared offset without a ZIP64 end record, as Info-ZIP's zip -fz writes it,
+ * tells nothing: shift = 0); and walks the central directory.  Per record it reads method, general-purpose flags, DOS
+ * time and date, CRC32, sizes, name, local header offset, external attributes and the ZIP64 extra field (0x0001: the
+ * values that are all-ones in the record, in the order size, compressed size, offset); other extra fields and the entry
+ * comment are skipped.  It fails with XLZ_ERR_UNSUPPORTED for a multi-disk archive (a disk number other than 0, entry
+ * counts that differ), XLZ_ERR_UNEXPECTED_EOF for a file shorter than an end record or a central directory that is cut
+ * (longer than what lies in front of the end record, or a record that leaves it), XLZ_ERR_RESULT where there is no end
+ * record, a locator leads to no ZIP64 end record, the directory would begin in front of its declared offset, a record has
+ * another signature, or the announced number of records does not fill the directory's size exactly.  Nothing else fails
+ * it: what is wrong with ONE entry is that entry's class.
+ *
+ * Every entry is resolved against its LOCAL header at open: that header must lie inside the file and carry PK\3\4,
+ * data_off = header_off + 30 + the local header's OWN name and extra lengths, and [data_off, data_off + comp_size) must
+ * lie in front of the central directory.  Sizes and CRC are the central directory's only (an entry written with a data
+ * descriptor, flag bit 3, has zeros in its local header).  A method-14 payload is 2 version bytes, a 2-byte little-endian
+ * property size that must be 5, the lc/lp/pb byte (< 225), a 4-byte dictionary size, then the raw stream; flag bit 1 says
+ * whether that stream ends in an end marker (decoded with the size unknown and out_cap = size) or at `size` (decoded with
+ * unpack_size = size).  The classes, fixed at open:
+ *   supported    method 0 (stored), or method 14 and well formed: XLZ_ZIP_ENTRY_SUPPORTED
+ *   unsupported  any other method (deflate 8, bzip2 12, xz 95, ...); encrypted (flag bit 0 or 6); patched data (bit 5);
+ *                method 0 with comp_size != size; a size or a payload above 0xFFFF0000 bytes ("4 GiB": what a unit's
+ *                32-bit counters hold): neither bit
+ *   bad          the local header is out of the file or without signature, or the ZIP64 extra field is too short
+ *                (data_off = 0); the data is out of bounds; the LZMA header is malformed (comp_size < 9, a property size
+ *                other than 5, a props byte >= 225): XLZ_ZIP_ENTRY_BAD
+ * A directory is an entry whose name ends in '/'; it has no bytes, whatever its fields say.  The handle BORROWS `file`
+ * until xlz_zip_close and never changes after open: any number of threads and contexts may use one at once.
+ *
+ * Names are handed out AS STORED, each NUL-terminated in one pool (UTF-8 where XLZ_ZIP_ENTRY_UTF8 is set, else by
+ * convention code page 437): no separator is normalised, no ".." removed.  The library writes no files; A CALLER THAT
+ * DOES MUST NOT TRUST A NAME AS A PATH.
+ *
+ * xlz_zip_extract_layout sets wants[i].dst_cap = the entry's size (0 for one without bytes) and dst_off = the next
+ * multiple of align (>= 1; 0: XLZ_ERR_BAD_ARG) behind the window before, in want order, *total = the end of the last window
+ * (XLZ_ERR_OUT_CAP: the windows do not fit 64 bits; XLZ_ERR_BAD_ARG: an entry index outside the table).
+ *
+ * xlz_zip_extract_device: the wanted method-14 entries are ONE batch (xlz_batch_create / run / results) whose
+ * descriptors point INTO the file image (in = file + data_off + 9, in_len = comp_size - 9): one decode launch sequence,
+ * however many entries.  With verify != 0 the CRC32 of every wanted entry is computed on the device by the check kernels,
+ * whatever the context's check mode: a method-14 entry as a range over its stream, a stored entry over its bytes where
+ * they lie in the destination.  ONE pack writes the method-14 entries into their windows.  Stored entries do not go up
+ * one copy each: host threads gather their bytes into ONE pinned staging block of the context's pool, each at an offset
+ * congruent to its destination modulo 16, the block goes up in one transfer together with its item table, and the pack
+ * kernel scatters it with the block as its source.  A block holds up to 256 MiB of stored bytes (one entry above that
+ * has a block to itself); xlz_zip_extract_stats::stored_uploads counts the transfers, 1 for anything smaller and never
+ * growing with the number of entries.  xlz_zip_extract: the same steps into a staging block of the context's pool that
+ * holds the wanted sizes back to back, one download, and a scatter of the good entries into the windows.
+ *
+ * Per wanted entry, in this order: an entry without bytes (a directory, size 0 -- a size-0 method-14 entry is not
+ * launched) is XLZ_OK with out_len 0, whatever its window and class; XLZ_ERR_OUT_CAP -- dst_cap is smaller than the entry
+ * (it then asks nothing of the batch); XLZ_ERR_UNSUPPORTED -- an unsupported entry; XLZ_ERR_RESULT -- a bad entry; the
+ * stream did not end with a status >= 0 and exactly `size` bytes: the stream's own status where that is negative, else
+ * XLZ_ERR_RESULT -- XLZ_ERR_OUT_CAP from an end-marker stream, which only wanted to go on behind the declared size, is
+ * reported as XLZ_ERR_RESULT -- and such a stream is left out of ranges and pack; XLZ_ERR_RESULT -- the CRC32 differs.
+ * out_len is 0 unless the status is XLZ_OK.  The same entry may be wanted twice, into two windows.
+ *
+ * INVARIANT: an entry's result in a call of many equals its result when it is extracted alone.
+ *
+ * The call returns XLZ_OK whenever it ran.  XLZ_ERR_BAD_ARG: NULL arguments with n > 0; an entry index outside the table;
+ * a window of an entry with bytes that does not fit out_cap; two such windows that share a byte (these are tested
+ * before the context is used; the window of an entry without bytes declares nothing); d_out that is not out_cap bytes of
+ * device memory of the context's device.  Such a call launches nothing, writes nothing -- results[] included -- and
+ * leaves every statistic as it was; an empty want list launches nothing either and is XLZ_OK.  Another negative status
+ * (XLZ_ERR_DEVICE): the call could not run, and every results[i].status is that status.  Bytes outside every window are
+ * never written; inside the window of a good entry nothing behind out_len is written.  The window of an entry that failed
+ * is untouched in the host form; in the device form it is untouched too unless the entry failed by its CRC32 alone, which
+ * is known only when its bytes lie there.  xlz_batch_advice tells when a handful of entries is the host's job; there is
+ * no fallback in here.                                                                                              */
+typedef struct xlz_zip_archive xlz_zip_archive;
+enum { XLZ_ZIP_ENTRY_SUPPORTED = 1, XLZ_ZIP_ENTRY_IS_DIR = 2, XLZ_ZIP_ENTRY_UTF8 = 4, XLZ_ZIP_ENTRY_ENCRYPTED = 8,
+       XLZ_ZIP_ENTRY_HAS_DESCRIPTOR = 16, XLZ_ZIP_ENTRY_ZIP64 = 32, XLZ_ZIP_ENTRY_BAD = 64, XLZ_ZIP_ENTRY_END_MARKER = 128 };
+typedef struct xlz_zip_entry { /* 72 bytes (the fields do not fit 64) */
+    uint64_t size, comp_size;      /* from the central directory                                           */
+    uint64_t header_off, data_off; /* shifted; data_off = 0 for a BAD entry whose header is unusable       */
+    uint64_t name_off;             /* into the name pool: bytes AS STORED, NUL-terminated                  */
+    uint32_t name_len, crc;        /* name_len: bytes, without the NUL                                     */
+    uint32_t dos_time_date;        /* time in the low, date in the high half                               */
+    uint32_t external_attr;
+    uint32_t dict_size;            /* method 14, well formed                                               */
+    uint16_t method, gp_flags;
+    uint8_t props, reserved[3];    /* props: method 14, well formed: the lc/lp/pb byte                     */
+    uint32_t flags;                /* XLZ_ZIP_ENTRY_*                                                      */
+} xlz_zip_entry;
+typedef struct xlz_zip_want {
+    uint64_t entry;                /* index into the entries                                               */
+    uint64_t dst_off, dst_cap;     /* its window [dst_off, dst_off + dst_cap) in the destination           */
+} xlz_zip_want;
+typedef struct xlz_zip_file_result {
+    int32_t status;
+    uint32_t reserved;
+    uint64_t out_len;              /* bytes at dst_off; 0 unless status == XLZ_OK                          */
+} xlz_zip_file_result;
+int xlz_zip_open(const uint8_t *file, size_t len, xlz_zip_archive **a); /* host only; the file must outlive a */
+void xlz_zip_close(xlz_zip_archive *a);
+/* every pointer but `a` may be NULL.  name_bytes: the size of the name pool; total_size: the sum of the sizes of the
+ * entries that have bytes; shift: the bytes in front of the archive                                                  */
+int xlz_zip_archive_info(const xlz_zip_archive *a, size_t *n_entries, size_t *name_bytes, uint64_t *total_size,
+                         uint64_t *shift);
+/* at most max_entries entries and names_cap bytes of the pool are copied; XLZ_ERR_OUT_CAP: there are more of either   */
+int xlz_zip_archive_entries(const xlz_zip_archive *a, xlz_zip_entry *entries, size_t max_entries, char *names,
+                            size_t names_cap);
+int xlz_zip_extract_layout(const xlz_zip_archive *a, xlz_zip_want *wants, size_t n, uint64_t align, uint64_t *total);
+int xlz_zip_extract(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_want *wants, size_t n, uint8_t *out,
+                    size_t out_cap, int verify, xlz_zip_file_result *results);
+int xlz_zip_extract_device(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_want *wants, size_t n, void *d_out,
+                           size_t out_cap, int verify, xlz_zip_file_result *results);
+/* Of the most recent xlz_zip_extract / xlz_zip_extract_device on `ctx` that ran: one that passed its argument tests and
+ * had a want list that is not empty.  Such a call starts the check and pack statistics over, fills them (the scatter of
+ * the stored entries counts as a pack launch), and publishes these at its end -- also when the device then failed it
+ * (XLZ_ERR_DEVICE: failed_entries == entries, copied_bytes 0).                                                       */
+typedef struct xlz_zip_extract_stats {
+    uint64_t entries, empty_entries; /* as wanted; of them without bytes                                  */
+    uint64_t failed_entries;         /* with a status other than XLZ_OK                                   */
+    uint64_t lzma_entries;           /* method-14 streams given to the batch                              */
+    uint64_t stored_entries;         /* stored entries gathered, uploaded and scattered                   */
+    uint64_t comp_bytes;             /* payload bytes of both kinds read from the file (comp_size)        */
+    uint64_t copied_bytes;           /* the sum of out_len                                                */
+    uint32_t stored_uploads;         /* host-to-device transfers made for the stored entries              */
+    uint32_t reserved;
+} xlz_zip_extract_stats;
+int xlz_ctx_last_zip_extract_stats(xlz_ctx *ctx, xlz_zip_extract_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

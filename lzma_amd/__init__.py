@@ -202,6 +202,16 @@ class Context:
             raise LzmaError(st, "xlz_ctx_last_7z_extract_stats")
         return {f: getattr(s, f) for f, _ in N.SzExtractStats._fields_}
 
+    def last_zip_extract_stats(self):
+        """of the most recent ZipFile extraction on this context that ran: entries, empty_entries, failed_entries,
+        lzma_entries (streams of the batch), stored_entries, comp_bytes, copied_bytes, stored_uploads (host-to-device
+        transfers made for the stored entries: 1 however many there are, as long as they fit one staging block)"""
+        s = N.ZipExtractStats()
+        st = N.lib().xlz_ctx_last_zip_extract_stats(self._h, ctypes.byref(s))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_zip_extract_stats")
+        return {f: getattr(s, f) for f, _ in N.ZipExtractStats._fields_ if f != "reserved"}
+
     def last_tar_stats(self):
         """of the most recent tar_scan_device / TarXzFile.list on this context whose scan ran: blocks, zero_blocks,
         candidate_blocks (downloaded), header_blocks (reached by the walk), meta_bytes, downloaded_bytes, kernel_ms, launches"""
@@ -1396,6 +1406,162 @@ class SevenZipFile:
     def close(self):
         if self._h:
             N.lib().xlz_7z_close(self._h)
+            self._h = ctypes.c_void_p()
+        if getattr(self, "_held", False):
+            self._held = False
+            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the entries of a .zip archive (include/xlz.h: xlz_zip_open / xlz_zip_extract / xlz_zip_extract_device) ----
+class ZipFile:
+    """The table of one .zip archive (xlz_zip_open; host only) and the extraction of chosen entries as ONE batch: every
+    wanted method-14 (LZMA) entry is a stream of one decode launch sequence, stored entries go up in one transfer, the
+    CRC32 of every entry is checked on the device.  `data` is bytes or any contiguous buffer; it is borrowed through the
+    buffer protocol, never copied, and held until close().  Raises LzmaError where the central directory cannot be walked
+    or the archive spans disks; what is wrong with one entry (deflate, encryption, a broken header) is that entry's
+    status when it is extracted.  .entries: one dict per entry with the fields of xlz_zip_entry, `name`, `mtime` (a tuple
+    like zipfile's date_time) and `supported`, `is_dir`, `bad`; .names: decoded as zipfile does, UTF-8 where flag bit 11
+    is set, else CP437.  Names are AS STORED in the archive: do not trust one as a path.  Read-only once made; a context
+    manager; close() may be repeated."""
+
+    def __init__(self, data):
+        self._h = ctypes.c_void_p()
+        self._view = _PyBuffer()
+        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:
+            raise TypeError("ZipFile needs bytes or a contiguous buffer")
+        self._held = True
+        try:
+            L = N.lib()
+            st = L.xlz_zip_open(ctypes.c_void_p(self._view.buf), self._view.len, ctypes.byref(self._h))
+            if st != OK:
+                self._h = ctypes.c_void_p()
+                raise LzmaError(st, "xlz_zip_open")
+            ne, nb, total, shift = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64(), ctypes.c_uint64()
+            L.xlz_zip_archive_info(self._h, ctypes.byref(ne), ctypes.byref(nb), ctypes.byref(total), ctypes.byref(shift))
+            ents = (N.ZipEntry * max(ne.value, 1))()
+            pool = ctypes.create_string_buffer(max(nb.value, 1))
+            st = L.xlz_zip_archive_entries(self._h, ents, ne.value, ctypes.cast(pool, ctypes.c_void_p), nb.value)
+            if st != OK:
+                raise LzmaError(st, "xlz_zip_archive_entries")
+        except Exception:
+            self.close()
+            raise
+        self.total_size, self.shift = total.value, shift.value
+        raw = pool.raw
+        fields = [f for f, _ in N.ZipEntry._fields_ if f not in ("reserved", "name_off", "name_len")]
+        self.entries = []
+        for i in range(ne.value):
+            x = ents[i]
+            d = {f: getattr(x, f) for f in fields}
+            stored = raw[x.name_off:x.name_off + x.name_len]
+            d["name"] = stored.decode("utf-8" if x.flags & N.ZIP_ENTRY_UTF8 else "cp437", "replace")
+            t, day = x.dos_time_date & 0xFFFF, x.dos_time_date >> 16
+            d["mtime"] = ((day >> 9) + 1980, (day >> 5) & 15, day & 31, t >> 11, (t >> 5) & 63, (t & 31) * 2)
+            d["supported"], d["is_dir"], d["bad"] = (bool(x.flags & N.ZIP_ENTRY_SUPPORTED), bool(x.flags & N.ZIP_ENTRY_IS_DIR),
+                                                     bool(x.flags & N.ZIP_ENTRY_BAD))
+            self.entries.append(d)
+        self.names = [e["name"] for e in self.entries]
+
+    def _handle(self):
+        if not self._h:
+            raise LzmaError(ERR_CLOSED, "ZipFile is closed")
+        return self._h
+
+    def index(self, which):
+        """an entry's index from an index or a name (the first entry of that name)"""
+        if isinstance(which, str):
+            try:
+                return self.names.index(which)
+            except ValueError:
+                raise KeyError(which)
+        return int(which)
+
+    def _list(self, which):
+        return [self.index(w) for w in ([which] if isinstance(which, (int, str)) else which)]
+
+    def _wants(self, wants):
+        arr = (N.ZipWant * max(len(wants), 1))()
+        for i, w in enumerate(wants):
+            arr[i].entry, arr[i].dst_off, arr[i].dst_cap = int(w[0]), int(w[1]), int(w[2])
+        return arr
+
+    def layout(self, which, align=1):
+        """xlz_zip_extract_layout: windows of the wanted entries back to back -> ([(entry, dst_off, dst_cap)], total)"""
+        idx = self._list(which)
+        arr = self._wants([(i, 0, 0) for i in idx])
+        total = ctypes.c_uint64()
+        st = N.lib().xlz_zip_extract_layout(self._handle(), arr, len(idx), int(align), ctypes.byref(total))
+        if st != OK:
+            raise LzmaError(st, "xlz_zip_extract_layout")
+        return [(arr[i].entry, arr[i].dst_off, arr[i].dst_cap) for i in range(len(idx))], total.value
+
+    def _extract(self, name, ctx, wants, dst, cap, verify):
+        res = (N.ZipFileResult * max(len(wants), 1))()
+        st = getattr(N.lib(), name)(ctx._h if ctx is not None else None, self._handle(), self._wants(wants), len(wants), dst, int(cap),
+                                    1 if verify else 0, res)
+        if st != OK:
+            raise LzmaError(st, name)
+        return [(res[i].status, res[i].out_len) for i in range(len(wants))]
+
+    def extract_into(self, ctx, wants, out, verify=True):
+        """xlz_zip_extract with the caller's buffer: wants = [(entry, dst_off, dst_cap)] into `out` (a writable buffer); the
+        windows of entries with bytes must not overlap -> [(status, out_len)]"""
+        dst = out if isinstance(out, ctypes.Array) else (ctypes.c_char * memoryview(out).nbytes).from_buffer(out)
+        return self._extract("xlz_zip_extract", ctx, wants, ctypes.cast(dst, ctypes.c_void_p), ctypes.sizeof(dst), verify)
+
+    def extract_device(self, ctx, wants, dptr, cap, verify=True):
+        """xlz_zip_extract_device: the same into `cap` bytes of device memory at the address `dptr` (on the context's device)"""
+        return self._extract("xlz_zip_extract_device", ctx, wants, ctypes.c_void_p(int(dptr)), cap, verify)
+
+    def extract(self, ctx, which, verify=True):
+        """the wanted entries (indices or names) as ONE batch -> [(status, bytes)], bytes empty unless the status is OK; only
+        what concerns the whole call is raised"""
+        wants, total = self.layout(which)
+        out = ctypes.create_string_buffer(max(total, 1))
+        res = self._extract("xlz_zip_extract", ctx, wants, ctypes.cast(out, ctypes.c_void_p), total, verify)
+        base = ctypes.addressof(out)
+        return [(st, ctypes.string_at(base + w[1], n) if st == OK else b"") for w, (st, n) in zip(wants, res)]
+
+    def read(self, ctx, which, verify=True):
+        """one entry's bytes (b"" for a directory); raises LzmaError on a failed entry"""
+        i = self.index(which)
+        st, got = self.extract(ctx, [i], verify=verify)[0]
+        if st != OK:
+            raise LzmaError(st, "xlz_zip_extract: entry %d" % i)
+        return got
+
+    def extract_tensor(self, ctx, which, verify=True, align=1, out=None):
+        """extract_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least the
+        layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(entry, off, out_len, status)]): an entry is
+        tensor[off:off + out_len] where its status is OK"""
+        import torch  # (only here: importing lzma_amd does not import torch)
+        dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
+        wants, total = self.layout(which, align)
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
+        elif out.numel() < total:
+            raise LzmaError(ERR_OUT_CAP, "the layout needs %d bytes, out holds %d" % (total, out.numel()))
+        torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
+        res = self.extract_device(ctx, wants, out.data_ptr(), out.numel(), verify=verify)
+        return out, [(w[0], w[1], n, st) for w, (st, n) in zip(wants, res)]
+
+    def close(self):
+        if self._h:
+            N.lib().xlz_zip_close(self._h)
             self._h = ctypes.c_void_p()
         if getattr(self, "_held", False):
             self._held = False

@@ -65,6 +65,8 @@ EXPORTS = [
     "xlz_7z_extract_layout", "xlz_7z_extract", "xlz_7z_extract_device", "xlz_ctx_last_7z_extract_stats",
     "xlz_tar_parse_host", "xlz_tar_scan_device", "xlz_xz_tar_list", "xlz_tar_info", "xlz_tar_entries", "xlz_tar_close",
     "xlz_ctx_last_tar_stats",
+    "xlz_zip_open", "xlz_zip_close", "xlz_zip_archive_info", "xlz_zip_archive_entries", "xlz_zip_extract_layout", "xlz_zip_extract",
+    "xlz_zip_extract_device", "xlz_ctx_last_zip_extract_stats",
 ]
 
 
@@ -234,6 +236,31 @@ class SzExtractStats(ctypes.Structure):
     _fields_ = [("entries", ctypes.c_uint64), ("empty_entries", ctypes.c_uint64), ("failed_entries", ctypes.c_uint64),
                 ("folders", ctypes.c_uint64), ("comp_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64),
                 ("folder_bytes", ctypes.c_uint64), ("copied_bytes", ctypes.c_uint64)]
+
+
+ZIP_ENTRY_SUPPORTED, ZIP_ENTRY_IS_DIR, ZIP_ENTRY_UTF8, ZIP_ENTRY_ENCRYPTED = 1, 2, 4, 8
+ZIP_ENTRY_HAS_DESCRIPTOR, ZIP_ENTRY_ZIP64, ZIP_ENTRY_BAD, ZIP_ENTRY_END_MARKER = 16, 32, 64, 128
+
+
+class ZipEntry(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint64), ("comp_size", ctypes.c_uint64), ("header_off", ctypes.c_uint64), ("data_off", ctypes.c_uint64),
+                ("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("dos_time_date", ctypes.c_uint32),
+                ("external_attr", ctypes.c_uint32), ("dict_size", ctypes.c_uint32), ("method", ctypes.c_uint16), ("gp_flags", ctypes.c_uint16),
+                ("props", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3), ("flags", ctypes.c_uint32)]
+
+
+class ZipWant(ctypes.Structure):
+    _fields_ = [("entry", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64)]
+
+
+class ZipFileResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
+
+
+class ZipExtractStats(ctypes.Structure):
+    _fields_ = [("entries", ctypes.c_uint64), ("empty_entries", ctypes.c_uint64), ("failed_entries", ctypes.c_uint64),
+                ("lzma_entries", ctypes.c_uint64), ("stored_entries", ctypes.c_uint64), ("comp_bytes", ctypes.c_uint64),
+                ("copied_bytes", ctypes.c_uint64), ("stored_uploads", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class TarEntry(ctypes.Structure):
@@ -478,6 +505,16 @@ def lib():
         L.xlz_tar_close.restype = None
         L.xlz_ctx_last_tar_stats.argtypes = [vp, ctypes.POINTER(TarStats)]
         L.xlz_internal_tar_classify_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.POINTER(ctypes.c_double)]
+    if hasattr(L, "xlz_zip_open"):  # (an older library loaded through XLZ_SO reads no .zip archives)
+        L.xlz_zip_open.argtypes = [vp, sz, ctypes.POINTER(vp)]
+        L.xlz_zip_close.argtypes = [vp]
+        L.xlz_zip_close.restype = None
+        L.xlz_zip_archive_info.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_zip_archive_entries.argtypes = [vp, ctypes.POINTER(ZipEntry), sz, vp, sz]
+        L.xlz_zip_extract_layout.argtypes = [vp, ctypes.POINTER(ZipWant), sz, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.xlz_zip_extract.argtypes = [vp, vp, ctypes.POINTER(ZipWant), sz, vp, sz, i32, ctypes.POINTER(ZipFileResult)]
+        L.xlz_zip_extract_device.argtypes = L.xlz_zip_extract.argtypes
+        L.xlz_ctx_last_zip_extract_stats.argtypes = [vp, ctypes.POINTER(ZipExtractStats)]
     _lib = L
     return L
 

@@ -18,6 +18,8 @@ void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s);
 void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s);
 // what xlz_ctx_last_7z_extract_stats reports: set by every xlz_7z_extract / xlz_7z_extract_device that ran
 void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s);
+// what xlz_ctx_last_zip_extract_stats reports: set by every xlz_zip_extract / xlz_zip_extract_device that ran
+void xlz_internal_zip_extract_stats_set(xlz_ctx *ctx, const xlz_zip_extract_stats &s);
 // the device steps of xlz_tar_scan_device (xlz_tar_dev.hip) on the context's stream: the flags of the image's complete
 // 512-byte blocks -> flags_out, and blocks idx[0 .. n) dense -> out_host; *ms = the kernel's time.  What
 // xlz_ctx_last_tar_stats reports is set by every scan that ran.
@@ -64,6 +66,15 @@ struct DeviceDest {
     // and, where want_in is given and want_in[i] is not kAnyInput, want_in[i] bytes of input used.
     const int32_t *want_status = nullptr;
     static constexpr uint64_t kAnyInput = ~(uint64_t)0;
+    // gather_copies (xlz_zip_extract: thousands of stored entries, and every small copy costs the stack some 12 us): the
+    // copies do not go up one by one behind everything else.  Host threads gather them into a pinned block of the
+    // context's pool, each at an offset congruent to its destination modulo 16, the block goes up in ONE transfer with
+    // its item table in front, and the pack kernel scatters it with the block as its source -- BEFORE the digests of the
+    // ranges over the destination, which may therefore cover copied bytes.  A block holds at most kGatherBlockBytes of
+    // copies (a longer copy has one to itself); *copy_uploads (optional) = the transfers made.  n may then be 0.
+    bool gather_copies = false;
+    uint32_t *copy_uploads = nullptr;
+    static constexpr uint64_t kGatherBlockBytes = 256ull << 20;
 };
 // a device block of at least `bytes` from the context's pool (xlz_7z_decode with a BCJ2 folder decodes into one), its
 // download into host memory once the context's stream has drained, and its return

@@ -257,6 +257,7 @@ struct xlz_ctx {
     xlz_xz_read_stats last_xz_read = {}; // xlz_ctx_last_xz_read_stats (xlz_xz.hip)
     xlz_xz_many_stats last_xz_many = {}; // xlz_ctx_last_xz_many_stats (xlz_xz.hip)
     xlz_7z_extract_stats last_7z_extract = {}; // xlz_ctx_last_7z_extract_stats (xlz_7z_extract.hip)
+    xlz_zip_extract_stats last_zip_extract = {}; // xlz_ctx_last_zip_extract_stats (xlz_zip.hip)
     xlz_tar_stats last_tar = {}; // xlz_ctx_last_tar_stats (xlz_tar_dev.hip)
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
@@ -2436,6 +2437,72 @@ void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats 
     std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->last_7z_extract = s;
 }
+// chosen entries of a .zip archive (xlz_zip.hip: xlz_zip_extract / xlz_zip_extract_device)
+extern "C" int xlz_ctx_last_zip_extract_stats(xlz_ctx *ctx, xlz_zip_extract_stats *out) { return last_stats(ctx, &xlz_ctx::last_zip_extract, out); }
+void xlz_internal_zip_extract_stats_set(xlz_ctx *ctx, const xlz_zip_extract_stats &s)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_zip_extract = s;
+}
+
+namespace {
+
+// DeviceDest::gather_copies: copies[0 .. n) (inside dest.cap, disjoint in the destination) through pinned blocks of the
+// context's pool.  A block is | item table, to a multiple of 256 | the copies' bytes in the order of their destinations,
+// each at the next offset congruent to its destination modulo 16 (the pack kernel's one-load path) | 64 bytes |; the
+// kernel's aligned loads around an item (xlz_pack_dev.h: load16) begin at or behind the byte area's first byte and end
+// inside those 64.  Every block is waited for before the next one is filled.  acc: the scatters as pack launches.
+int gather_copies_run(xlz_ctx *ctx, const DeviceDest &dest, hipStream_t stream, uint32_t *uploads, xlz_pack_stats &acc)
+{
+    using xlzpack::DevItem;
+    const uint64_t mis = (uintptr_t)dest.d_dst & 15;
+    std::vector<size_t> order;
+    for (size_t k = 0; k < dest.n_copies; k++)
+        if (dest.copies[k].len) order.push_back(k);
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return dest.copies[x].dst_off < dest.copies[y].dst_off; });
+    for (size_t k0 = 0; k0 < order.size();) {
+        std::vector<DevItem> tab;
+        uint64_t at = 0, payload = 0;
+        size_t k1 = k0;
+        for (; k1 < order.size(); k1++) {
+            const DeviceCopy &c = dest.copies[order[k1]];
+            if (k1 > k0 && payload + c.len > DeviceDest::kGatherBlockBytes) break;
+            at += ((c.dst_off + mis) - at) & 15;
+            tab.push_back(DevItem{at, c.dst_off + mis, c.len});
+            at += c.len, payload += c.len;
+        }
+        if (tab.size() > 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+        const size_t tab_bytes = (tab.size() * sizeof(DevItem) + 255) / 256 * 256, total = tab_bytes + (size_t)at + 64;
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        uint8_t *pin = static_cast<uint8_t *>(ctx->pool.take(total, true)), *dev = static_cast<uint8_t *>(ctx->pool.take(total, false));
+        int st = pin && dev && !((uintptr_t)dev & 15) ? XLZ_OK : XLZ_ERR_DEVICE;
+        if (st == XLZ_OK) {
+            memcpy(pin, tab.data(), tab.size() * sizeof(DevItem));
+            constexpr size_t kGroup = 64; // copies per turn of a thread
+            xlzpost::parallel_for((tab.size() + kGroup - 1) / kGroup, xlzpost::host_thread_cap(8), [&](size_t g) {
+                for (size_t j = g * kGroup; j < tab.size() && j < (g + 1) * kGroup; j++)
+                    memcpy(pin + tab_bytes + tab[j].src, dest.copies[order[k0 + j]].src, (size_t)tab[j].len);
+            });
+            if (hipMemcpyAsync(dev, pin, total - 64, hipMemcpyHostToDevice, stream) != hipSuccess) st = XLZ_ERR_DEVICE;
+        }
+        if (st == XLZ_OK) {
+            if (uploads) ++*uploads;
+            if (xlz::pack_launch(dev + tab_bytes, (uint64_t)at + 64, static_cast<uint8_t *>(dest.d_dst) - mis, reinterpret_cast<const DevItem *>(dev),
+                                 (uint32_t)tab.size(), xlzpack::first_tile(tab.data()), xlzpack::tile_count(tab.data(), (uint32_t)tab.size()),
+                                 ctx->num_cus, stream) != 0)
+                st = XLZ_ERR_DEVICE;
+        }
+        if (hipStreamSynchronize(stream) != hipSuccess && st == XLZ_OK) st = XLZ_ERR_DEVICE;
+        ctx->pool.give(pin), ctx->pool.give(dev);
+        if (st != XLZ_OK) return st;
+        acc.items += tab.size(), acc.bytes += payload, acc.congruent_items += tab.size(), acc.launches++;
+        k0 = k1;
+    }
+    return XLZ_OK;
+}
+
+} // namespace
 
 // ---------------------------------------------------------------- .tar members of an image in device memory ----
 // The two device steps of xlz_tar_scan_device (xlz_tar_dev.hip), on the context's stream with scratch from its pool; each
@@ -3573,7 +3640,7 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         uint64_t at;
         if (r.stream != xlzpost::kDestStream)
             of_streams.push_back(q);
-        else if (r.kind == XLZ_CHECK_SHA256 || !n || !xlzpost::dest_resolve(r.off, r.len, dest.cap, 0, &at))
+        else if (r.kind == XLZ_CHECK_SHA256 || (!n && !dest.gather_copies) || !xlzpost::dest_resolve(r.off, r.len, dest.cap, 0, &at))
             return XLZ_ERR_BAD_ARG;
         else
             of_dest.push_back(q);
@@ -3645,10 +3712,25 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
             st = batch_bcj2_run(b, dest.bcj2, dest.n_bcj2, dest.d_dst, dest.bcj2_res, stream, dest.bcj2_mode == 2 ? 2 : 1, bj);
             if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_bcj2, bj, true);
         }
-        if (st == XLZ_OK) digests(of_dest, &dest);
+        if (st == XLZ_OK && !dest.gather_copies) digests(of_dest, &dest);
     }
     if (hipSetDevice(ctx->device) != hipSuccess) st = st == XLZ_OK ? XLZ_ERR_DEVICE : st;
-    for (size_t k = 0; k < dest.n_copies && st == XLZ_OK; k++)
+    if (dest.gather_copies && st == XLZ_OK) { // the copies as one transfer per block and a scatter, then the digests that may cover them
+        xlz_pack_stats pk = {};
+        st = gather_copies_run(ctx, dest, stream, dest.copy_uploads, pk);
+        if (st == XLZ_OK && pk.launches) publish(ctx, &xlz_ctx::last_pack, pk, true);
+        if (st == XLZ_OK && !of_dest.empty()) {
+            if (!b) { // (no stream in the call: a batch of none, for the check kernels' scratch alone)
+                b = new (std::nothrow) xlz_batch;
+                if (b) b->ctx = ctx, b->pooled = true, b->quiet = true; // (everything on the stream has been waited for)
+            }
+            if (b)
+                digests(of_dest, &dest);
+            else
+                st = XLZ_ERR_DEVICE;
+        }
+    }
+    for (size_t k = 0; k < dest.n_copies && st == XLZ_OK && !dest.gather_copies; k++)
         if (dest.copies[k].len && hipMemcpyAsync(static_cast<uint8_t *>(dest.d_dst) + dest.copies[k].dst_off, dest.copies[k].src,
                                                  (size_t)dest.copies[k].len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
             st = XLZ_ERR_DEVICE;
