@@ -1,5 +1,8 @@
 // The device checks' 64-lane scheme (lzma_amd/csrc/xlz_check_dev.h) run lane by lane on the CPU against a bit-by-bit
 // CRC: what the kernels of xlz_check_dev.hip compute, without a GPU.  Prints "ok" and exits 0, or says what differs.
+//   check_dev_selftest                        the built-in sweep
+//   check_dev_selftest --list LIST ARENA OUT  the scheme over the ranges LIST names in the bytes of ARENA (list_mode below):
+//                                             tests/test_digest_edges_cpu.py judges the digests in OUT
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -105,8 +108,44 @@ template <int W> static int run()
     return bad;
 }
 
-int main()
+// --list: one range per line of LIST, "KIND OFF LEN" (KIND 1 = CRC32, 4 = CRC64; OFF + LEN inside ARENA), through
+// Scheme::range; OUT receives eight bytes per line, the digest zero-extended, little-endian
+static int list_mode(const char *list_path, const char *arena_path, const char *out_path)
 {
+    std::vector<uint8_t> arena;
+    FILE *f = fopen(arena_path, "rb");
+    if (!f) return 2;
+    if (fseek(f, 0, SEEK_END) != 0) return 2;
+    const long size = ftell(f);
+    if (size < 0 || fseek(f, 0, SEEK_SET) != 0) return 2;
+    arena.resize((size_t)size);
+    if (size && fread(arena.data(), 1, arena.size(), f) != arena.size()) return 2;
+    fclose(f);
+    FILE *list = fopen(list_path, "r"), *out = fopen(out_path, "wb");
+    if (!list || !out) return 2;
+    static const Scheme<32> S32;
+    static const Scheme<64> S64;
+    unsigned long kind;
+    unsigned long long off, len;
+    while (fscanf(list, "%lu %llu %llu", &kind, &off, &len) == 3) {
+        if ((kind != 1 && kind != 4) || off > arena.size() || len > arena.size() - off) return 2;
+        const uint64_t d = kind == 1 ? S32.range(arena.data(), off, len) : S64.range(arena.data(), off, len);
+        uint8_t b[8];
+        for (int k = 0; k < 8; k++) b[k] = (uint8_t)(d >> (8 * k));
+        if (fwrite(b, 1, 8, out) != 8) return 2;
+    }
+    const bool all_read = feof(list) != 0;
+    fclose(list);
+    return fclose(out) == 0 && all_read ? 0 : 2;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc == 5 && !strcmp(argv[1], "--list")) return list_mode(argv[2], argv[3], argv[4]);
+    if (argc != 1) {
+        printf("usage: check_dev_selftest [--list LIST ARENA OUT]\n");
+        return 2;
+    }
     const int bad = run<32>() + run<64>();
     if (bad) {
         printf("%d differences\n", bad);

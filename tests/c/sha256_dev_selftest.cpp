@@ -1,6 +1,9 @@
 // One lane of the device's SHA-256 (lzma_amd/csrc/xlz_sha256_dev.h) run on the CPU against the FIPS 180-4 known answers
 // and the host's xlzcheck::sha256: what xlz_check_sha256_kernel computes per range, without a GPU.  Prints "ok" and exits
 // 0, or says what differs.
+//   sha256_dev_selftest                        the built-in sweep
+//   sha256_dev_selftest --list LIST ARENA OUT  the lane's code over the ranges LIST names in the bytes of ARENA (list_mode
+//                                              below): tests/test_digest_edges_cpu.py judges the digests in OUT
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -60,8 +63,41 @@ static void against_host(const std::vector<uint8_t> &arena, uint64_t arena_bytes
     }
 }
 
-int main()
+// --list: one range per line of LIST, "KIND OFF LEN" (KIND 10 = SHA-256; OFF + LEN inside ARENA), through lane_digest and
+// digest_word with the file's size as arena_bytes; OUT receives the 32 bytes the kernel would store per line
+static int list_mode(const char *list_path, const char *arena_path, const char *out_path)
 {
+    std::vector<uint8_t> arena;
+    FILE *f = fopen(arena_path, "rb");
+    if (!f) return 2;
+    if (fseek(f, 0, SEEK_END) != 0) return 2;
+    const long size = ftell(f);
+    if (size < 0 || fseek(f, 0, SEEK_SET) != 0) return 2;
+    arena.resize((size_t)size);
+    if (size && fread(arena.data(), 1, arena.size(), f) != arena.size()) return 2;
+    fclose(f);
+    FILE *list = fopen(list_path, "r"), *out = fopen(out_path, "wb");
+    if (!list || !out) return 2;
+    unsigned long kind;
+    unsigned long long off, len;
+    while (fscanf(list, "%lu %llu %llu", &kind, &off, &len) == 3) {
+        if (kind != 10 || off > arena.size() || len > arena.size() - off) return 2;
+        uint8_t d[32];
+        lane(arena.data(), arena.size(), off, len, d);
+        if (fwrite(d, 1, 32, out) != 32) return 2;
+    }
+    const bool all_read = feof(list) != 0;
+    fclose(list);
+    return fclose(out) == 0 && all_read ? 0 : 2;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc == 5 && !strcmp(argv[1], "--list")) return list_mode(argv[2], argv[3], argv[4]);
+    if (argc != 1) {
+        printf("usage: sha256_dev_selftest [--list LIST ARENA OUT]\n");
+        return 2;
+    }
     known("empty", {}, "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855");
     known("abc", {'a', 'b', 'c'}, "ba7816bf8f01cfea414140de5dae2223b00361a396177a9cb410ff61f20015ad");
     {
