@@ -88,8 +88,14 @@ def _head_vectors(lane, dpp=True, lay=None):
     return [np.array(x, dtype=np.uint32) for x in (hc, hms, hm2, litnext)]
 
 
+SENTINEL = 0xA5     # fills the output buffer from `size` on: the loop stores nothing there
+
+
 def run_fast_loop(program, payload, lc, lp, pb, dict_size, size, expect, dpp=True, strict_waits=False, base=0):
-    """-> (bytes decoded by the emulated loop, machine, number of loop entries, exits by code)"""
+    """-> (bytes decoded by the emulated loop, machine, number of loop entries, exits by code, input position).
+    `size` is the room of the output AND bytesLeft (lzma_run takes the smaller of the two): the buffer behind it is filled
+    with SENTINEL, and neither the loop nor a copy it hands back (cut to the bytes that are left, as lzma_run cuts it, and
+    the last thing this harness does) stores anything at or beyond `size`."""
     from gcn_emu import Machine
     final, sizes, layout = program
     m = Machine(final, sizes, layout.SGPR_OPS, layout.VGPR_OPS, layout.SGPR64_OPS)
@@ -99,7 +105,7 @@ def run_fast_loop(program, payload, lc, lp, pb, dict_size, size, expect, dpp=Tru
     n_probs = lay["P_LIT"] + (0x100 << (lc + lp))
     m.lds[0:2 * n_probs:2] = 0x00
     m.lds[1:2 * n_probs:2] = 0x04          # every probability 1024 (state.go:79-121)
-    out = bytearray(size + 1024)
+    out = bytearray(size) + bytes([SENTINEL]) * 1024
     out[:base] = expect[:base]              # (base > 0: an LZMA2 unit whose dictionary epoch starts at `base`)
     mp = bytearray(b"\x00\x04" * (256 + ((0x400 if "mlv" in getattr(program, "variant", ()) else 0x200) << (lc + lp))))
     m.mem["outp"], m.mem["mptr"] = out, mp
@@ -138,14 +144,19 @@ def run_fast_loop(program, payload, lc, lp, pb, dict_size, size, expect, dpp=Tru
         assert bytes(out[pos0:s["pos"]]) == expect[pos0:s["pos"]], "bytes differ behind position %d" % pos0
         if ec == 3:                         # a copy the loop leaves to its caller (wave_copy)
             n, dist = s["lenout"], s["rep0"] + 1
+            cut = n > size - s["pos"]
+            n = min(n, size - s["pos"])      # (lzma_run: truncated to bytesLeft / to the room; the unit ends there)
             for i in range(n):
                 out[s["pos"] + i] = out[s["pos"] + i - dist] if s["pos"] + i >= dist + base else 0
             s["pos"] += n
             s["wpos"] = (s["wpos"] + n) % dict_size
             s["prev"] = out[s["pos"] - 1]
             s["mb"] = out[s["pos"] - dist] if s["pos"] >= dist + base else 0
+            if cut:
+                break
         elif ec != 0:
             break
+    assert out[size:] == bytes([SENTINEL]) * 1024, "the loop stored at or beyond the end of the output"
     return bytes(out[base:s["pos"]]) if base else bytes(out[:s["pos"]]), m, entries, exits, p
 
 
