@@ -5,6 +5,13 @@
 // guards untouched.  Every stream lies in a heap block of exactly its length rounded up to 16, so an address sanitizer sees
 // any load the header's alignment rule does not cover.
 //   g++ -O2 -std=c++17 -I lzma_amd/csrc tests/c/bcj2_dev_selftest.cpp -o t && ./t [file of machine code]
+//   ./t --merge-list LIST IN OUT   the wave scheme on items somebody else made (tests/bcj2_edges.py): LIST holds a line
+//                                  "MAIN CALL JUMP RC OUT_LEN RESIDUE KEEP" per item -- the lengths of its four streams,
+//                                  which lie end to end in IN, its out_len, the residue modulo 16 of its destination, and
+//                                  KEEP = 1 for an item that finds the Wave as the item before it left it (what a
+//                                  workgroup's second item finds; 0: filled with A5).  OUT receives per item a status byte
+//                                  (0 OK, 1 XLZ_ERR_RESULT) and, for status 0, the out_len bytes.  Exit status 3: the
+//                                  wave and host_merge disagree, or a guard byte was written.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -123,10 +130,10 @@ struct Block {
     ~Block() { free(p); }
 };
 
-static DevResult wave_run(const DevItem &it, uint8_t *dst)
+static DevResult wave_run(const DevItem &it, uint8_t *dst, bool keep = false)
 {
     static Wave w;
-    memset(&w, 0xA5, sizeof w);
+    if (!keep) memset(&w, 0xA5, sizeof w);
     for (int l = kLanes - 1; l >= 0; l--) wave_init(w, it, (uint32_t)l);
     while (!w.done) {
         for (int l = kLanes - 1; l >= 0; l--) wave_load(w, it, (uint32_t)l);
@@ -139,7 +146,8 @@ static DevResult wave_run(const DevItem &it, uint8_t *dst)
 }
 
 // host_merge and the wave on the same four streams and out_len, the wave at destination offset dst_off (any alignment)
-static void compare(const char *what, const Enc &e, size_t out_len, const Bytes *expect, int expect_status, uint32_t dst_off)
+static void compare(const char *what, const Enc &e, size_t out_len, const Bytes *expect, int expect_status, uint32_t dst_off, bool keep = false,
+                    FILE *report = nullptr)
 {
     g_cases++;
     Bytes ho(out_len + 1, 0xCC);
@@ -160,7 +168,7 @@ static void compare(const char *what, const Enc &e, size_t out_len, const Bytes 
     it.main = bm.p, it.call = bc.p, it.jump = bj.p, it.rc = br.p;
     it.main_len = (uint32_t)e.main.size(), it.call_len = (uint32_t)e.call.size(), it.jump_len = (uint32_t)e.jump.size(), it.rc_len = (uint32_t)e.rc.size();
     it.dst = kGuard + dst_off, it.out_len = (uint32_t)out_len;
-    const DevResult r = wave_run(it, base);
+    const DevResult r = wave_run(it, base, keep);
     CHECK(r.status == hs, "%s: wave status %d, host_merge %d (out_len %zu, dst_off %u)", what, r.status, hs, out_len, dst_off);
     if (hs == kStOk && r.status == kStOk) // (how far a failed merge came is not part of the contract)
         CHECK(r.produced == hp && !memcmp(base + it.dst, ho.data(), out_len), "%s: wave bytes differ (out_len %zu, dst_off %u)", what, out_len, dst_off);
@@ -168,6 +176,10 @@ static void compare(const char *what, const Enc &e, size_t out_len, const Bytes 
     for (size_t i = 0; i < it.dst; i++) guards = guards && base[i] == 0x5A;
     for (size_t i = it.dst + out_len; i < span; i++) guards = guards && base[i] == 0x5A;
     CHECK(guards, "%s: wave wrote outside its range (out_len %zu, dst_off %u)", what, out_len, dst_off);
+    if (report) {
+        fputc(r.status == kStOk ? 0 : 1, report);
+        if (r.status == kStOk && out_len) fwrite(base + it.dst, 1, out_len, report);
+    }
     free(raw);
 }
 
@@ -230,8 +242,34 @@ static Bytes plain(size_t n)
     return v;
 }
 
+// --merge-list: see the head of this file
+static int merge_list(const char *list_path, const char *in_path, const char *out_path)
+{
+    FILE *list = fopen(list_path, "r"), *in = fopen(in_path, "rb"), *out = fopen(out_path, "wb");
+    if (!list || !in || !out) return 2;
+    unsigned long len[4], out_len, res, keep;
+    char what[32];
+    while (fscanf(list, "%lu %lu %lu %lu %lu %lu %lu", &len[0], &len[1], &len[2], &len[3], &out_len, &res, &keep) == 7) {
+        if (res > 15 || keep > 1) return 2;
+        Enc e;
+        Bytes *s[4] = {&e.main, &e.call, &e.jump, &e.rc};
+        for (int k = 0; k < 4; k++) {
+            s[k]->resize(len[k]);
+            if (len[k] && fread(s[k]->data(), 1, len[k], in) != len[k]) return 2;
+        }
+        snprintf(what, sizeof what, "item %ld", g_cases);
+        compare(what, e, out_len, nullptr, 1, (uint32_t)res, keep != 0, out);
+    }
+    const bool rest = fgetc(in) != EOF;
+    fclose(list), fclose(in);
+    if (fclose(out) != 0 || rest) return 2;
+    printf("%ld items, %d failures\n", g_cases, g_fail);
+    return g_fail ? 3 : 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 5 && !strcmp(argv[1], "--merge-list")) return merge_list(argv[2], argv[3], argv[4]);
     static const size_t lens[] = {0, 1, 4, 5, 6, 15, 16, 17, 1023, 1024, 1025, 2047, 2048, 2049, 5000, 65539};
     for (size_t n : lens)
         for (int policy = 0; policy < 4; policy++)

@@ -69,10 +69,44 @@ void run(const char *what, const Arena &A, std::vector<DevItem> items, uint64_t 
     }
 }
 
+// --pack-list LIST: tables somebody else made (tests/pack_edges.py), as Batch.pack takes them.  LIST holds, per table, a line
+// "STREAMS ITEMS DST_CAP MIS", the STREAMS sizes of the streams and ITEMS lines "STREAM OFF LEN DST_OFF".  The arena is laid
+// out as the library lays it out; the destination is MIS + DST_CAP bytes and 64 guard bytes from a multiple of 16 on, the
+// caller's pointer MIS behind its first byte: every tile of the launch, against memcpy per item, the whole of it compared.
+int pack_list(const char *path)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) return 2;
+    unsigned long long n_streams, n_items, dst_cap, mis;
+    int tables = 0;
+    while (fscanf(f, "%llu %llu %llu %llu", &n_streams, &n_items, &dst_cap, &mis) == 4) {
+        if (mis > 15) return 2;
+        std::vector<uint64_t> caps;
+        for (unsigned long long k = 0, c; k < n_streams; k++) {
+            if (fscanf(f, "%llu", &c) != 1) return 2;
+            caps.push_back(c);
+        }
+        const Arena A(caps);
+        std::vector<DevItem> items;
+        for (uint64_t i = 0; i < n_items; i++) {
+            unsigned long long s, off, len, dst;
+            if (fscanf(f, "%llu %llu %llu %llu", &s, &off, &len, &dst) != 4 || s >= n_streams || off > caps[s] || len > caps[s] - off) return 2;
+            items.push_back(DevItem{A.region[s] + off, dst + mis, len});
+        }
+        char what[48];
+        snprintf(what, sizeof what, "table %d (mis %llu)", tables++, mis);
+        run(what, A, items, mis + dst_cap + 64);
+    }
+    fclose(f);
+    printf("%d tables, %d failures\n", tables, failures);
+    return failures ? 3 : 0;
+}
+
 } // namespace
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc == 3 && !strcmp(argv[1], "--pack-list")) return pack_list(argv[2]);
     // every (source mod 16, destination mod 16) pair x lengths 0-48: each alone, and all of a length in one table
     {
         Arena A({4096});

@@ -9,7 +9,6 @@ import os
 import random
 import zlib
 
-import numpy as np
 import pytest
 
 import corpus
@@ -20,11 +19,11 @@ import sevenzip_craft as C
 import xz_chains as X
 from lzma_amd import FMT_LZMA2_RAW, LzmaError
 from lzma_amd import _native as N
+from pack_edges import FILL, expect_pack
 
 pytestmark = pytest.mark.gpu
 
 DICT = 1 << 16
-FILL = 0xA5
 SIZES = ([0] + list(range(1, 19)) + [31, 33, 255, 256, 257] + list(range(4095, 4102)) + list(range(16379, 16390)) +
          list(range(65531, 65542)) + [(1 << 20) + 16385, 3_000_001])
 L2 = {"id": lzma.FILTER_LZMA2}
@@ -91,26 +90,6 @@ def plan_items(sizes):
         dst += 10
     random.Random(99).shuffle(items)
     return items, dst + 33
-
-
-def expect_pack(items, plains, cap, ptr_mod):
-    """what the pack must leave in a destination of `cap` bytes filled with FILL whose address is ptr_mod modulo 16
-    -> (bytes, copied per item, statistics)"""
-    want = np.full(cap, FILL, dtype=np.uint8)
-    copied = []
-    st = {"items": 0, "bytes": 0, "congruent_items": 0, "empty_items": 0}
-    for k, off, length, dst in items:
-        n = len(plains[k])
-        lo, hi = min(off, n), min(off + length, n)
-        copied.append(hi - lo)
-        if hi == lo:
-            st["empty_items"] += 1
-            continue
-        want[dst:dst + hi - lo] = np.frombuffer(plains[k], dtype=np.uint8)[lo:hi]
-        st["items"] += 1
-        st["bytes"] += hi - lo
-        st["congruent_items"] += lo % 16 == (ptr_mod + dst) % 16
-    return want.tobytes(), copied, st
 
 
 def test_pack_of_a_device_resident_batch(ctx, streams300):

@@ -9,8 +9,10 @@ import os
 import random
 import sys
 import tarfile
+import time
 
 import pytest
+import torch   # (before libxlz.so is loaded: torch brings its own HIP runtime, which must be the one that initialises the device)
 
 import lzma_amd
 from lzma_amd import LzmaError
@@ -253,3 +255,50 @@ def test_tar_xz_file_on_a_damaged_block_and_an_empty_archive(ctx, twelve_blocks)
             f.list(ctx)
         assert e.value.status == N.ERR_UNEXPECTED_EOF and len(f.entries) == 2
         assert len(f.list(ctx, strict=False)) == 2
+
+
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def test_classify_kernel_over_many_rounds(ctx, mixed_image):
+    """an image of three times as many blocks as one round of the grid takes (8 workgroups per CU x 8 pairs x 2 blocks), and
+    more: the fixture's 8191 blocks tiled -- an odd number, so every repetition shifts which half of a pair a header falls
+    in -- and 511 trailing bytes.  The flags are the fixture's flags tiled: no block is judged again"""
+    t_start = time.time()
+    data, want = mixed_image
+    cus = _cus()
+    reps = -(-(3 * 128 * cus + 1) // 8191)
+    blocks = 8191 * reps
+    assert blocks >= 3 * 128 * cus + 1
+    image = data[:512 * 8191] * reps + data[512 * 8191:]
+    assert len(image) == 512 * blocks + 511
+    t, ptr = _upload(image)
+    st, flags, ms = _classify(ctx, ptr, len(image))
+    print("classify: %d blocks = %d pairs on %d CUs, %d pairs per round: %.2f rounds; kernel %.3f ms"
+          % (blocks, -(-blocks // 2), cus, 64 * cus, -(-blocks // 2) / (64.0 * cus), ms))
+    assert st == N.OK and ms > 0
+    assert flags[:blocks] == want * reps
+    assert flags[blocks] == 0xEE  # no flag for the partial block
+    assert _bytes(t) == bytes([0xA5]) * GUARD + image + bytes([0xA5]) * GUARD  # the image and its guards are only read
+    print("test_classify_kernel_over_many_rounds: %.1f s wall" % (time.time() - t_start))
+
+
+def test_gather_kernel_over_many_rounds(ctx):
+    """an archive of three times as many header blocks as one round of the gather's grid takes (8 workgroups per CU x 256
+    threads, a thread per 16 bytes: 64 blocks per CU), and one more: empty members, every block a candidate"""
+    t_start = time.time()
+    cus = _cus()
+    members = 3 * 64 * cus + 1
+    assert members >= 3 * 64 * cus + 1
+    image = b"".join(T.header(b"many/%07d.txt" % i, mtime=T.MTIME + i, mode=0o600 + i % 64) for i in range(members)) + bytes(1024)
+    t, ptr = _upload(image)
+    table = lzma_amd.tar_scan_device(ctx, ptr, len(image))
+    s = ctx.last_tar_stats()
+    print("gather: %d candidate blocks on %d CUs, %d blocks per round: %.2f rounds; stats %s" % (members, cus, 64 * cus, members / (64.0 * cus), s))
+    assert table == lzma_amd.tar_parse(image) and table.end_status == N.OK and len(table.entries) == members
+    assert T.rows(table.entries) == T.judge(image)
+    assert s["candidate_blocks"] == members == s["header_blocks"] and (s["blocks"], s["zero_blocks"]) == (members + 2, 2)
+    assert s["launches"] == 2 and s["meta_bytes"] == 0
+    assert _bytes(t) == bytes([0xA5]) * GUARD + image + bytes([0xA5]) * GUARD
+    print("test_gather_kernel_over_many_rounds: %.1f s wall" % (time.time() - t_start))
