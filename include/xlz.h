@@ -490,6 +490,63 @@ typedef struct xlz_bcj2_stats {
 } xlz_bcj2_stats;
 int xlz_ctx_last_bcj2_stats(xlz_ctx *ctx, xlz_bcj2_stats *out);
 
+/* ---- raw deflate streams (lzma_amd/csrc/xlz_inflate_dev.hip) ----
+ * Outside the reference.  Deflate (RFC 1951) is method 8 of a .zip archive: what nearly every archive uses.  A stream is
+ * decoded by ONE wave -- symbol decode wave-uniform, tables and input window in LDS, the lanes carrying literals, matches
+ * and stored blocks --, and the window is the output itself in device memory (the statement of the format, of the wave
+ * scheme and of what is which error is at the head of lzma_amd/csrc/xlz_inflate_dev.h).  Written from the RFC; the
+ * classes of failure are those of zlib 1.2.11, the first defect in stream order deciding:
+ *   XLZ_OK                  the final block's end-of-block was reached; input behind it is ignored, *consumed / in_consumed
+ *                           says where it stopped (the byte that holds the last bit included)
+ *   XLZ_ERR_RESULT          invalid data: block type 3, LEN / NLEN mismatch, too many length or distance symbols, a bad
+ *                           repeat, an over-subscribed or incomplete set of code lengths as zlib judges them, no
+ *                           end-of-block code, an invalid literal/length or distance code, a distance too far back
+ *   XLZ_ERR_UNEXPECTED_EOF  the input ends first
+ *   XLZ_ERR_OUT_CAP         the output would pass out_cap
+ * On a failure produced is 0 and the item's own range holds unspecified bytes.  No zlib or gzip wrapper is read.        */
+/* The serial decoder over host buffers: host only, no device needed.  XLZ_ERR_BAD_ARG: a NULL pointer with a length
+ * behind it.  produced and consumed may be NULL.                                                            */
+int xlz_inflate_host(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *produced, size_t *consumed);
+typedef struct xlz_inflate_item {
+    const uint8_t *in;  /* host memory: the stream                                                               */
+    uint64_t in_len;
+    uint64_t dst_off;   /* where its output goes in the destination                                              */
+    uint64_t dst_cap;   /* the room there                                                                        */
+} xlz_inflate_item;
+typedef struct xlz_inflate_result {
+    uint64_t produced;    /* 0 unless XLZ_OK                                                                     */
+    uint64_t in_consumed; /* 0 unless XLZ_OK                                                                     */
+    int32_t status;
+    uint32_t reserved;
+} xlz_inflate_result;
+/* Inflates every item into ONE caller-owned device buffer: host threads gather the inputs into one pinned block of the
+ * context's pool, each at a padded offset that is a multiple of 16, the block goes up in one transfer with the item table
+ * in front (xlz_inflate_stats::uploads stays 1 below 256 MiB of input), one launch sequence writes every item straight
+ * into d_dst + dst_off, and the call waits.  One bad item never fails the call.  XLZ_ERR_BAD_ARG, with nothing written:
+ * NULL arguments with n > 0; an item without a pointer to its length; an item's [dst_off, dst_off + dst_cap) does not fit
+ * in dst_cap; the ranges of two items share a byte; d_dst is not device memory of the context's device, or dst_cap
+ * reaches past its allocation.  n = 0 is XLZ_OK.  Nothing outside the items' ranges is written.  An item whose input or
+ * room is longer than the launch-length cap (0.5 s of one wave: xlzinf::kMaxDeviceLen) or 0xFFFF0000 bytes and more, and
+ * every item in deflate mode 2, is inflated by xlz_inflate_host's code on host threads and uploaded.  The call itself does
+ * not look at whether the mode is 0.                                                                        */
+int xlz_inflate_batch(xlz_ctx *ctx, const xlz_inflate_item *items, size_t n, void *d_dst, size_t dst_cap, xlz_inflate_result *results);
+/* What xlz_zip_extract / xlz_zip_extract_device do with deflate entries (XLZ_ZIP_ENTRY_DEFLATE).  0 (default): they refuse
+ * them (XLZ_ERR_UNSUPPORTED), as ever.  1: they inflate them on the device, in the same call as the LZMA batch and the
+ * stored scatter.  2: as 1, but on host threads, uploaded -- the fallback path and the A/B yardstick.  Any other value:
+ * XLZ_ERR_BAD_ARG.                                                                                          */
+int xlz_ctx_set_deflate_mode(xlz_ctx *ctx, int mode);
+int xlz_ctx_deflate_mode(const xlz_ctx *ctx);
+/* Of the most recent xlz_inflate_batch on `ctx`, or of the most recent xlz_zip_extract / xlz_zip_extract_device in deflate
+ * mode 1 / 2 that had a deflate entry to inflate.                                                            */
+typedef struct xlz_inflate_stats {
+    uint64_t device_items, device_bytes; /* inflated by the kernel (bytes of output of the good ones)          */
+    uint64_t host_items, host_bytes;     /* inflated on host threads: mode 2, or longer than the cap           */
+    uint64_t failed_items;               /* of either: status < 0                                              */
+    uint32_t uploads;                    /* transfers of gathered inputs                                       */
+    uint32_t launches;
+} xlz_inflate_stats;
+int xlz_ctx_last_inflate_stats(xlz_ctx *ctx, xlz_inflate_stats *out);
+
 /* ---- pull-style readers mirroring the reference's Go surface --------------- */
 /* Constructors take the compressed stream as a buffer (a Go shim slurps its io.Reader
  * first) and copy it.  Constructor-time errors are the ones the reference's
@@ -1101,6 +1158,9 @@ int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *s);
  *   bad          the local header is out of the file or without signature, or the ZIP64 extra field is too short
  *                (data_off = 0); the data is out of bounds; the LZMA header is malformed (comp_size < 9, a property size
  *                other than 5, a props byte >= 225): XLZ_ZIP_ENTRY_BAD
+ *   deflate      XLZ_ZIP_ENTRY_DEFLATE, a bit of its own beside the classes, which are set exactly as above (a deflate
+ *                entry is unsupported: neither bit): method 8, not encrypted or patched, local header and data in bounds,
+ *                size and payload below 0xFFFF0000 bytes.  Method 9 (Deflate64) never has it.
  * A directory is an entry whose name ends in '/'; it has no bytes, whatever its fields say.  The handle BORROWS `file`
  * until xlz_zip_close and never changes after open: any number of threads and contexts may use one at once.
  *
@@ -1143,10 +1203,24 @@ int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *s);
  * never written; inside the window of a good entry nothing behind out_len is written.  The window of an entry that failed
  * is untouched in the host form; in the device form it is untouched too unless the entry failed by its CRC32 alone, which
  * is known only when its bytes lie there.  xlz_batch_advice tells when a handful of entries is the host's job; there is
- * no fallback in here.                                                                                              */
+ * no fallback in here.
+ *
+ * DEFLATE ENTRIES (xlz_ctx_set_deflate_mode; 0, the default: everything above, a deflate entry is XLZ_ERR_UNSUPPORTED).
+ * In deflate mode 1 / 2 a wanted XLZ_ZIP_ENTRY_DEFLATE entry is an item of xlz_inflate_batch's machinery in the same call,
+ * behind the LZMA batch and the stored scatter and in front of the CRC32s: mode 1 on the device, mode 2 on host threads;
+ * in the device form written straight into its window, in the host form into the staging block.  With verify its CRC32
+ * is taken by the check kernels over the bytes where they lie, as for a stored entry.  Its verdict, in this order: what
+ * settles an entry before the batch, as above (XLZ_ERR_OUT_CAP for a window smaller than the entry); the inflate status
+ * where it is negative -- XLZ_ERR_OUT_CAP, which only says that the stream wanted to go on behind the declared size, as
+ * XLZ_ERR_RESULT, as for end-marker streams --; XLZ_ERR_RESULT unless exactly `size` bytes were produced; XLZ_ERR_RESULT
+ * when the CRC32 differs.  The INVARIANT holds for them.  The one difference: in the device form the window of a deflate
+ * entry that FAILED holds unspecified bytes, because it was decoded in place.  xlz_zip_extract_stats keeps its layout:
+ * entries, failed_entries, comp_bytes and copied_bytes count deflate entries, lzma_entries and stored_entries do not; the
+ * rest is in xlz_ctx_last_inflate_stats.                                                                              */
 typedef struct xlz_zip_archive xlz_zip_archive;
 enum { XLZ_ZIP_ENTRY_SUPPORTED = 1, XLZ_ZIP_ENTRY_IS_DIR = 2, XLZ_ZIP_ENTRY_UTF8 = 4, XLZ_ZIP_ENTRY_ENCRYPTED = 8,
-       XLZ_ZIP_ENTRY_HAS_DESCRIPTOR = 16, XLZ_ZIP_ENTRY_ZIP64 = 32, XLZ_ZIP_ENTRY_BAD = 64, XLZ_ZIP_ENTRY_END_MARKER = 128 };
+       XLZ_ZIP_ENTRY_HAS_DESCRIPTOR = 16, XLZ_ZIP_ENTRY_ZIP64 = 32, XLZ_ZIP_ENTRY_BAD = 64, XLZ_ZIP_ENTRY_END_MARKER = 128,
+       XLZ_ZIP_ENTRY_DEFLATE = 256 };
 typedef struct xlz_zip_entry { /* 72 bytes (the fields do not fit 64) */
     uint64_t size, comp_size;      /* from the central directory                                           */
     uint64_t header_off, data_off; /* shifted; data_off = 0 for a BAD entry whose header is unusable       */

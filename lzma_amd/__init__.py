@@ -18,6 +18,7 @@ from ._native import (EOF, ERR_BAD_ARG, ERR_CLOSED, ERR_DEVICE, ERR_HEADER_EOF, 
 
 # the .xz filter ids (include/xlz.h: XLZ_FILTER_*)
 FILTER_DELTA, FILTER_X86, FILTER_POWERPC, FILTER_IA64, FILTER_ARM, FILTER_ARMTHUMB, FILTER_SPARC = 3, 4, 5, 6, 7, 8, 9
+ZIP_ENTRY_DEFLATE = N.ZIP_ENTRY_DEFLATE  # xlz_zip_entry.flags: a method-8 entry that deflate mode 1 / 2 inflates
 
 
 class LzmaError(Exception):
@@ -192,6 +193,29 @@ class Context:
         if st != OK:
             raise LzmaError(st, "xlz_ctx_set_bcj2_mode")
 
+    def set_deflate_mode(self, mode):
+        """what ZipFile extractions do with deflate (method 8) entries (xlz_ctx_set_deflate_mode): 0 refuse them (default),
+        1 inflate them on the device, 2 the same on host threads"""
+        st = N.lib().xlz_ctx_set_deflate_mode(self._h, int(mode))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_set_deflate_mode")
+
+    def deflate_mode(self):
+        L = N.lib()
+        if not hasattr(L, "xlz_ctx_deflate_mode"):  # (an older library loaded through XLZ_SO: it refuses every deflate entry)
+            return 0
+        return L.xlz_ctx_deflate_mode(self._h)
+
+    def last_inflate_stats(self):
+        """what was inflated where in the last inflate_batch, or in the last ZipFile extraction in deflate mode 1 / 2 that had
+        a deflate entry, on this context (xlz_ctx_last_inflate_stats) -> dict: device_items, device_bytes, host_items,
+        host_bytes, failed_items, uploads, launches"""
+        s = N.InflateStats()
+        st = N.lib().xlz_ctx_last_inflate_stats(self._h, ctypes.byref(s))
+        if st != OK:
+            raise LzmaError(st, "xlz_ctx_last_inflate_stats")
+        return {k: getattr(s, k) for k, _ in N.InflateStats._fields_}
+
     def last_7z_extract_stats(self):
         """of the most recent SevenZipFile extraction on this context that ran: entries, empty_entries, failed_entries,
         folders, comp_bytes, decoded_bytes (what the batch was asked to decode), folder_bytes (the covering folders' full
@@ -361,6 +385,38 @@ def bcj2_host(main, call, jump, rc, out_len):
     if st != OK:
         raise LzmaError(st, "xlz_bcj2_host")
     return out.raw[: int(out_len)]
+
+
+def inflate_host(data, out_cap):
+    """a raw deflate stream (RFC 1951, no zlib or gzip wrapper) on the host -> (bytes, input bytes used) (xlz_inflate_host; no
+    device needed).  Raises LzmaError: ERR_RESULT invalid data, ERR_UNEXPECTED_EOF the input ends first, ERR_OUT_CAP more
+    than out_cap bytes"""
+    buf, p = _cbuf(data)
+    out = ctypes.create_string_buffer(max(int(out_cap), 1))
+    produced, consumed = ctypes.c_size_t(), ctypes.c_size_t()
+    st = N.lib().xlz_inflate_host(p, len(data), ctypes.cast(out, ctypes.c_void_p), int(out_cap), ctypes.byref(produced), ctypes.byref(consumed))
+    if st != OK:
+        raise LzmaError(st, "xlz_inflate_host")
+    return out.raw[: produced.value], consumed.value
+
+
+def inflate_batch(ctx, items, dptr, cap):
+    """raw deflate streams into one device buffer, each by one wave (xlz_inflate_batch; in deflate mode 2 on host threads).
+    items: [(stream bytes, dst_off, dst_cap), ...]; dptr / cap: device memory of the context's device
+    -> [(status, produced, in_consumed), ...]"""
+    items = list(items)
+    n = len(items)
+    arr = (N.InflateItem * max(n, 1))()
+    keep = []
+    for q, (data, dst_off, dst_cap) in enumerate(items):
+        buf, p = _cbuf(data)
+        keep.append(buf)
+        arr[q].inp, arr[q].in_len, arr[q].dst_off, arr[q].dst_cap = p, len(data), int(dst_off), int(dst_cap)
+    res = (N.InflateResult * max(n, 1))()
+    st = N.lib().xlz_inflate_batch(ctx._h, arr, n, ctypes.c_void_p(int(dptr)), int(cap), res)
+    if st != OK:
+        raise LzmaError(st, "xlz_inflate_batch")
+    return [(res[q].status, res[q].produced, res[q].in_consumed) for q in range(n)]
 
 
 def decode_batch_filtered(ctx, streams, steps, checks=()):
@@ -1432,7 +1488,8 @@ class ZipFile:
     buffer protocol, never copied, and held until close().  Raises LzmaError where the central directory cannot be walked
     or the archive spans disks; what is wrong with one entry (deflate, encryption, a broken header) is that entry's
     status when it is extracted.  .entries: one dict per entry with the fields of xlz_zip_entry, `name`, `mtime` (a tuple
-    like zipfile's date_time) and `supported`, `is_dir`, `bad`; .names: decoded as zipfile does, UTF-8 where flag bit 11
+    like zipfile's date_time) and `supported`, `is_dir`, `bad`, `deflate` (method 8 and well formed: extracted in the
+    context's deflate mode 1 / 2, refused in mode 0; `supported` is false for it as ever); .names: decoded as zipfile does, UTF-8 where flag bit 11
     is set, else CP437.  Names are AS STORED in the archive: do not trust one as a path.  Read-only once made; a context
     manager; close() may be repeated."""
 
@@ -1471,6 +1528,7 @@ class ZipFile:
             d["mtime"] = ((day >> 9) + 1980, (day >> 5) & 15, day & 31, t >> 11, (t >> 5) & 63, (t & 31) * 2)
             d["supported"], d["is_dir"], d["bad"] = (bool(x.flags & N.ZIP_ENTRY_SUPPORTED), bool(x.flags & N.ZIP_ENTRY_IS_DIR),
                                                      bool(x.flags & N.ZIP_ENTRY_BAD))
+            d["deflate"] = bool(x.flags & N.ZIP_ENTRY_DEFLATE)
             self.entries.append(d)
         self.names = [e["name"] for e in self.entries]
 

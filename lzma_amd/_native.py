@@ -67,6 +67,7 @@ EXPORTS = [
     "xlz_ctx_last_tar_stats",
     "xlz_zip_open", "xlz_zip_close", "xlz_zip_archive_info", "xlz_zip_archive_entries", "xlz_zip_extract_layout", "xlz_zip_extract",
     "xlz_zip_extract_device", "xlz_ctx_last_zip_extract_stats",
+    "xlz_inflate_host", "xlz_inflate_batch", "xlz_ctx_set_deflate_mode", "xlz_ctx_deflate_mode", "xlz_ctx_last_inflate_stats",
 ]
 
 
@@ -240,6 +241,21 @@ class SzExtractStats(ctypes.Structure):
 
 ZIP_ENTRY_SUPPORTED, ZIP_ENTRY_IS_DIR, ZIP_ENTRY_UTF8, ZIP_ENTRY_ENCRYPTED = 1, 2, 4, 8
 ZIP_ENTRY_HAS_DESCRIPTOR, ZIP_ENTRY_ZIP64, ZIP_ENTRY_BAD, ZIP_ENTRY_END_MARKER = 16, 32, 64, 128
+ZIP_ENTRY_DEFLATE = 256  # method 8 and well formed: what deflate mode 1 / 2 inflates (beside the classes, which it leaves alone)
+
+
+class InflateItem(ctypes.Structure):
+    _fields_ = [("inp", ctypes.c_void_p), ("in_len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64)]
+
+
+class InflateResult(ctypes.Structure):
+    _fields_ = [("produced", ctypes.c_uint64), ("in_consumed", ctypes.c_uint64), ("status", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class InflateStats(ctypes.Structure):
+    _fields_ = [("device_items", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_items", ctypes.c_uint64),
+                ("host_bytes", ctypes.c_uint64), ("failed_items", ctypes.c_uint64), ("uploads", ctypes.c_uint32),
+                ("launches", ctypes.c_uint32)]
 
 
 class ZipEntry(ctypes.Structure):
@@ -505,6 +521,12 @@ def lib():
         L.xlz_tar_close.restype = None
         L.xlz_ctx_last_tar_stats.argtypes = [vp, ctypes.POINTER(TarStats)]
         L.xlz_internal_tar_classify_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.POINTER(ctypes.c_double)]
+    if hasattr(L, "xlz_inflate_host"):  # (an older library loaded through XLZ_SO inflates nothing)
+        L.xlz_inflate_host.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.xlz_inflate_batch.argtypes = [vp, ctypes.POINTER(InflateItem), sz, vp, sz, ctypes.POINTER(InflateResult)]
+        L.xlz_ctx_set_deflate_mode.argtypes = [vp, i32]
+        L.xlz_ctx_deflate_mode.argtypes = [vp]
+        L.xlz_ctx_last_inflate_stats.argtypes = [vp, ctypes.POINTER(InflateStats)]
     if hasattr(L, "xlz_zip_open"):  # (an older library loaded through XLZ_SO reads no .zip archives)
         L.xlz_zip_open.argtypes = [vp, sz, ctypes.POINTER(vp)]
         L.xlz_zip_close.argtypes = [vp]

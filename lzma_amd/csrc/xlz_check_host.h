@@ -75,6 +75,14 @@ struct DeviceDest {
     bool gather_copies = false;
     uint32_t *copy_uploads = nullptr;
     static constexpr uint64_t kGatherBlockBytes = 256ull << 20;
+    // raw deflate streams (xlz_zip_extract in deflate mode 1 / 2; with gather_copies only): items as xlz_inflate_batch takes
+    // them, inflated into d_dst behind the scatter of the copies and in front of the digests of the ranges over the
+    // destination, which may therefore cover them; inflate_res[] their outcomes, inflate_mode 1: on the device, 2: on host
+    // threads.  One that failed does not end the call.  n may then be 0.
+    const xlz_inflate_item *inflate = nullptr;
+    size_t n_inflate = 0;
+    xlz_inflate_result *inflate_res = nullptr;
+    int inflate_mode = 1;
 };
 // a device block of at least `bytes` from the context's pool (xlz_7z_decode with a BCJ2 folder decodes into one), its
 // download into host memory once the context's stream has drained, and its return

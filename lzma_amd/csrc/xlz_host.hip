@@ -34,6 +34,7 @@
 #include "xlz_filter_dev.h"
 #include "xlz_pack_dev.h"
 #include "xlz_bcj2_dev.h"
+#include "xlz_inflate_dev.h"
 #include "xlz_7z_files.h"
 #include "xlz_xz_many.h"
 
@@ -262,6 +263,9 @@ struct xlz_ctx {
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
     xlz_bcj2_stats last_bcj2 = {};
+    // raw deflate streams (xlz_inflate_dev.hip): xlz_ctx_set_deflate_mode, xlz_ctx_last_inflate_stats
+    int deflate_mode = 0;
+    xlz_inflate_stats last_inflate = {};
 };
 
 // Scratch of one kind of post-decode kernel of a batch: device and pinned memory from where the batch's memory comes
@@ -2804,6 +2808,168 @@ extern "C" int xlz_ctx_last_bcj2_stats(xlz_ctx *ctx, xlz_bcj2_stats *out) { retu
 
 void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_bcj2, xlz_bcj2_stats{}, false); }
 
+// ---------------------------------------------------------------- raw deflate streams ----
+namespace xlz {
+int inflate_launch(const xlzinf::DevItem *items, uint32_t n_items, uint8_t *dst, xlzinf::DevResult *results, int num_cus, hipStream_t stream);
+}
+
+namespace {
+
+constexpr uint64_t kInflateBlockBytes = 256ull << 20; // of gathered inputs in one upload (an item above that has a block to itself)
+static_assert(xlzinf::kStOk == XLZ_OK && xlzinf::kStResult == XLZ_ERR_RESULT && xlzinf::kStEof == XLZ_ERR_UNEXPECTED_EOF &&
+                  xlzinf::kStOutCap == XLZ_ERR_OUT_CAP,
+              "xlz_inflate_dev.h names the statuses of include/xlz.h");
+
+void inflate_stats_set(xlz_ctx *ctx, const xlz_inflate_stats &s)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->last_inflate = s;
+}
+
+// xlz_inflate_batch's table as the caller declares it (cf. bcj2_items_ok)
+bool inflate_items_ok(const xlz_inflate_item *items, size_t n, uint64_t dst_cap)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> win;
+    for (size_t i = 0; i < n; i++) {
+        const xlz_inflate_item &it = items[i];
+        if (!it.in && it.in_len) return false;
+        if (it.dst_off > dst_cap || it.dst_cap > dst_cap - it.dst_off) return false;
+        if (it.dst_cap) win.emplace_back(it.dst_off, it.dst_off + it.dst_cap);
+    }
+    std::sort(win.begin(), win.end());
+    for (size_t i = 1; i < win.size(); i++)
+        if (win[i - 1].second > win[i].first) return false;
+    return true;
+}
+
+// Inflates items[0 .. n) (accepted by inflate_items_ok) into d_dst and waits: by the kernel on `stream` (mode 1, items up
+// to xlzinf::kMaxDeviceLen and below 0xFFFF0000 bytes in and out), the others by xlzinf::host_inflate on host threads,
+// uploaded afterwards.  The device's items go up longest first, in blocks of | item table, to a multiple of 256 | the
+// inputs, each at a multiple of 16 and padded to one | results |: ONE transfer and one launch per block.
+int inflate_run(xlz_ctx *ctx, const xlz_inflate_item *items, size_t n, void *d_dst, xlz_inflate_result *results, hipStream_t stream, int mode,
+                xlz_inflate_stats &acc)
+{
+    using namespace xlzinf;
+    if (!n) return XLZ_OK;
+    std::vector<size_t> on_dev, on_host;
+    for (size_t i = 0; i < n; i++) {
+        const xlz_inflate_item &it = items[i];
+        results[i] = xlz_inflate_result{0, 0, XLZ_OK, 0};
+        const bool small = it.in_len <= kMaxDeviceLen && it.dst_cap <= kMaxDeviceLen && it.in_len < kMaxUnitBytes && it.dst_cap < kMaxUnitBytes;
+        (mode == 1 && small ? on_dev : on_host).push_back(i);
+    }
+    std::stable_sort(on_dev.begin(), on_dev.end(), [&](size_t x, size_t y) { return items[x].in_len > items[y].in_len; });
+    for (size_t k0 = 0; k0 < on_dev.size();) {
+        uint64_t payload = 0;
+        size_t k1 = k0;
+        for (; k1 < on_dev.size() && k1 - k0 < 0xFFFFFFFFull; k1++) {
+            const uint64_t len = padded(items[on_dev[k1]].in_len);
+            if (k1 > k0 && payload + len > kInflateBlockBytes) break;
+            payload += len;
+        }
+        const size_t cnt = k1 - k0, tab_bytes = (cnt * sizeof(DevItem) + 255) / 256 * 256, res_off = tab_bytes + (size_t)payload,
+                     res_bytes = cnt * sizeof(DevResult), total = res_off + res_bytes;
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        uint8_t *pin = static_cast<uint8_t *>(ctx->pool.take(total, true)), *dev = static_cast<uint8_t *>(ctx->pool.take(total, false));
+        int st = pin && dev && !((uintptr_t)dev & 15) ? XLZ_OK : XLZ_ERR_DEVICE;
+        if (st == XLZ_OK) {
+            DevItem *tab = reinterpret_cast<DevItem *>(pin);
+            uint64_t at = tab_bytes;
+            for (size_t q = 0; q < cnt; q++) {
+                const xlz_inflate_item &it = items[on_dev[k0 + q]];
+                tab[q].in = dev + at, tab[q].in_len = (uint32_t)it.in_len, tab[q].out_cap = (uint32_t)it.dst_cap, tab[q].dst = it.dst_off;
+                at += padded(it.in_len);
+            }
+            constexpr size_t kGroup = 64; // inputs per turn of a thread
+            xlzpost::parallel_for((cnt + kGroup - 1) / kGroup, xlzpost::host_thread_cap(8), [&](size_t g) {
+                for (size_t q = g * kGroup; q < cnt && q < (g + 1) * kGroup; q++) {
+                    const xlz_inflate_item &it = items[on_dev[k0 + q]];
+                    if (it.in_len) memcpy(pin + (tab[q].in - dev), it.in, (size_t)it.in_len);
+                }
+            });
+            if (hipMemcpyAsync(dev, pin, res_off, hipMemcpyHostToDevice, stream) != hipSuccess) st = XLZ_ERR_DEVICE;
+        }
+        if (st == XLZ_OK) {
+            acc.uploads++;
+            if (xlz::inflate_launch(reinterpret_cast<const DevItem *>(dev), (uint32_t)cnt, static_cast<uint8_t *>(d_dst),
+                                    reinterpret_cast<DevResult *>(dev + res_off), ctx->num_cus, stream) != 0)
+                st = XLZ_ERR_DEVICE;
+        }
+        if (st == XLZ_OK && hipMemcpyAsync(pin + res_off, dev + res_off, res_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess) st = XLZ_ERR_DEVICE;
+        if (hipStreamSynchronize(stream) != hipSuccess && st == XLZ_OK) st = XLZ_ERR_DEVICE;
+        if (st == XLZ_OK) {
+            const DevResult *res = reinterpret_cast<const DevResult *>(pin + res_off);
+            for (size_t q = 0; q < cnt; q++) {
+                xlz_inflate_result &r = results[on_dev[k0 + q]];
+                const bool ok = res[q].status == kStOk && res[q].produced <= items[on_dev[k0 + q]].dst_cap;
+                r.status = ok ? (int32_t)XLZ_OK : res[q].status < 0 ? res[q].status : (int32_t)XLZ_ERR_RESULT;
+                r.produced = ok ? res[q].produced : 0, r.in_consumed = ok ? res[q].consumed : 0;
+                acc.device_items++, acc.device_bytes += r.produced, acc.failed_items += !ok;
+            }
+            acc.launches++;
+        }
+        ctx->pool.give(pin), ctx->pool.give(dev);
+        if (st != XLZ_OK) return st;
+        k0 = k1;
+    }
+    if (!on_host.empty()) {
+        std::vector<std::vector<uint8_t>> out(on_host.size());
+        xlzpost::parallel_for(on_host.size(), xlzpost::host_thread_cap(16), [&](size_t q) {
+            const xlz_inflate_item &it = items[on_host[q]];
+            xlz_inflate_result &r = results[on_host[q]];
+            out[q].resize((size_t)it.dst_cap);
+            size_t produced = 0, consumed = 0;
+            r.status = host_inflate(it.in, (size_t)it.in_len, out[q].data(), out[q].size(), &produced, &consumed);
+            r.produced = produced, r.in_consumed = consumed;
+        });
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (size_t q = 0; q < on_host.size(); q++) {
+            const xlz_inflate_item &it = items[on_host[q]];
+            const xlz_inflate_result &r = results[on_host[q]];
+            if (r.status == XLZ_OK && r.produced)
+                HIP_TRY(hipMemcpy(static_cast<uint8_t *>(d_dst) + it.dst_off, out[q].data(), (size_t)r.produced, hipMemcpyHostToDevice));
+            acc.host_items++, acc.host_bytes += r.produced, acc.failed_items += r.status != XLZ_OK;
+        }
+    }
+    return XLZ_OK;
+}
+
+} // namespace
+
+extern "C" int xlz_inflate_host(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *produced, size_t *consumed)
+{
+    if (produced) *produced = 0;
+    if (consumed) *consumed = 0;
+    if ((!in && in_len) || (!out && out_cap)) return XLZ_ERR_BAD_ARG;
+    return xlzinf::host_inflate(in, in_len, out, out_cap, produced, consumed);
+}
+
+extern "C" int xlz_inflate_batch(xlz_ctx *ctx, const xlz_inflate_item *items, size_t n, void *d_dst, size_t dst_cap, xlz_inflate_result *results)
+{
+    if (!ctx) return XLZ_ERR_BAD_ARG;
+    if (!n) return XLZ_OK;
+    if (!items || !results || !d_dst || !inflate_items_ok(items, n, dst_cap)) return XLZ_ERR_BAD_ARG;
+    const int ok = device_dst_ok(ctx, d_dst, dst_cap);
+    if (ok != XLZ_OK) return ok;
+    xlz_inflate_stats acc = {};
+    const int st = inflate_run(ctx, items, n, d_dst, results, ctx->stream, xlz_ctx_deflate_mode(ctx) == 2 ? 2 : 1, acc);
+    if (st == XLZ_OK) inflate_stats_set(ctx, acc);
+    return st;
+}
+
+extern "C" int xlz_ctx_set_deflate_mode(xlz_ctx *ctx, int mode)
+{
+    if (!ctx || mode < 0 || mode > 2) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->deflate_mode = mode;
+    return XLZ_OK;
+}
+extern "C" int xlz_ctx_deflate_mode(const xlz_ctx *ctx) { return ctx ? ctx->deflate_mode : XLZ_ERR_BAD_ARG; }
+extern "C" int xlz_ctx_last_inflate_stats(xlz_ctx *ctx, xlz_inflate_stats *out) { return last_stats(ctx, &xlz_ctx::last_inflate, out); }
+
 int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p)
 {
     if (!ctx || !p) return XLZ_ERR_BAD_ARG;
@@ -3654,6 +3820,8 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         if (dest.copies[k].dst_off > dest.cap || dest.copies[k].len > dest.cap - dest.copies[k].dst_off) return XLZ_ERR_BAD_ARG;
     if (!xlzpost::pack_items_ok(items.data(), items.size(), n, dest.cap)) return XLZ_ERR_BAD_ARG;
     if (dest.n_bcj2 && (!n || !dest.bcj2 || !dest.bcj2_res || !bcj2_items_ok(dest.bcj2, dest.n_bcj2, n, dest.cap))) return XLZ_ERR_BAD_ARG;
+    if (dest.n_inflate && (!dest.gather_copies || !dest.inflate || !dest.inflate_res || !inflate_items_ok(dest.inflate, dest.n_inflate, dest.cap)))
+        return XLZ_ERR_BAD_ARG;
     if (dest.cap) {
         const int ok = device_dst_ok(ctx, dest.d_dst, dest.cap);
         if (ok != XLZ_OK) return ok;
@@ -3719,6 +3887,11 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         xlz_pack_stats pk = {};
         st = gather_copies_run(ctx, dest, stream, dest.copy_uploads, pk);
         if (st == XLZ_OK && pk.launches) publish(ctx, &xlz_ctx::last_pack, pk, true);
+        if (st == XLZ_OK && dest.n_inflate) { // the deflate entries: inflated into the destination, then checked THERE
+            xlz_inflate_stats inf = {};
+            st = inflate_run(ctx, dest.inflate, dest.n_inflate, dest.d_dst, dest.inflate_res, stream, dest.inflate_mode == 2 ? 2 : 1, inf);
+            if (st == XLZ_OK) inflate_stats_set(ctx, inf);
+        }
         if (st == XLZ_OK && !of_dest.empty()) {
             if (!b) { // (no stream in the call: a batch of none, for the check kernels' scratch alone)
                 b = new (std::nothrow) xlz_batch;

@@ -26,7 +26,7 @@ namespace xlzzip {
 constexpr size_t kEndLen = 22, kLocatorLen = 20, kEnd64Len = 56, kCentralLen = 46, kLocalLen = 30;
 constexpr size_t kEndSearch = kEndLen + 65535; // the end record and the longest comment: where the search ends
 constexpr uint32_t kSigEnd = 0x06054b50, kSigLocator = 0x07064b50, kSigEnd64 = 0x06064b50, kSigCentral = 0x02014b50, kSigLocal = 0x04034b50;
-constexpr uint16_t kStored = 0, kLzma = 14;
+constexpr uint16_t kStored = 0, kDeflate = 8, kLzma = 14;
 constexpr size_t kLzmaHead = 9; // method 14: version (2), property size (2) = 5, lc/lp/pb (1), dictionary size (4)
 constexpr uint64_t kMaxDeviceEntry = 0xFFFF0000ull; // what a unit's 32-bit counters hold (xlz_7z_files.h: kMaxDeviceFolder)
 constexpr uint64_t kDestStream = ~(uint64_t)0;      // xlz_post.h: a check range over the destination
@@ -190,6 +190,9 @@ inline void resolve(const uint8_t *f, size_t len, const End &e, bool bad64, xlz_
     }
     if (bad) x.flags |= XLZ_ZIP_ENTRY_BAD;
     if (!bad && !unsupported(x)) x.flags |= XLZ_ZIP_ENTRY_SUPPORTED;
+    // a bit beside the classes, which stay as they were: what deflate mode 1 / 2 inflates (open has no context to ask)
+    if (!bad && x.method == kDeflate && !(x.gp_flags & (1u | 1u << 5 | 1u << 6)) && x.size < kMaxDeviceEntry && x.comp_size < kMaxDeviceEntry)
+        x.flags |= XLZ_ZIP_ENTRY_DEFLATE;
 }
 
 struct Table {
@@ -273,10 +276,13 @@ struct Plan {
     std::vector<xlz_pack_item> items;     // as streams: the whole stream -> dst[want]
     std::vector<Span> spans;              // the wanted stored entries that are left
     std::vector<size_t> span_want;        // as spans: the want
+    std::vector<xlz_inflate_item> inflate; // deflate mode 1 / 2: the wanted deflate entries that are left, INTO the file -> dst[want]
+    std::vector<size_t> inflate_want;      // as inflate: the want
 };
 
-// dst[i]: where want i's bytes go (the window's dst_off, or its place in the staging block)
-inline void plan(const uint8_t *file, const xlz_zip_entry *e, const xlz_zip_want *w, const uint64_t *dst, size_t n, Plan &p)
+// dst[i]: where want i's bytes go (the window's dst_off, or its place in the staging block).  deflate_mode 0: a deflate
+// entry is unsupported, as every entry of another method is
+inline void plan(const uint8_t *file, const xlz_zip_entry *e, const xlz_zip_want *w, const uint64_t *dst, size_t n, Plan &p, int deflate_mode = 0)
 {
     p = Plan{};
     p.pre.assign(n, XLZ_OK);
@@ -285,6 +291,8 @@ inline void plan(const uint8_t *file, const xlz_zip_entry *e, const xlz_zip_want
         if (!has_bytes(x)) continue;
         if (w[i].dst_cap < x.size) {
             p.pre[i] = XLZ_ERR_OUT_CAP;
+        } else if (deflate_mode && (x.flags & XLZ_ZIP_ENTRY_DEFLATE)) {
+            p.inflate.push_back(xlz_inflate_item{file + x.data_off, x.comp_size, dst[i], x.size}), p.inflate_want.push_back(i);
         } else if (unsupported(x)) {
             p.pre[i] = XLZ_ERR_UNSUPPORTED;
         } else if (x.flags & XLZ_ZIP_ENTRY_BAD) {
@@ -305,7 +313,7 @@ inline void plan(const uint8_t *file, const xlz_zip_entry *e, const xlz_zip_want
 }
 
 // The CRC32 ranges of a verifying call and per want its range (kNone: none): a method-14 entry over its stream, a stored
-// entry over its bytes where they lie in the destination.
+// or a deflate entry over its bytes where they lie in the destination.
 inline void check_ranges(const Plan &p, size_t n, std::vector<xlz_check_range> &cr, std::vector<size_t> &range_of)
 {
     cr.clear(), range_of.assign(n, kNone);
@@ -320,6 +328,10 @@ inline void check_ranges(const Plan &p, size_t n, std::vector<xlz_check_range> &
         c.stream = kDestStream, c.off = p.spans[k].dst, c.len = p.spans[k].len;
         range_of[p.span_want[k]] = cr.size(), cr.push_back(c);
     }
+    for (size_t k = 0; k < p.inflate.size(); k++) {
+        c.stream = kDestStream, c.off = p.inflate[k].dst_off, c.len = p.inflate[k].dst_cap;
+        range_of[p.inflate_want[k]] = cr.size(), cr.push_back(c);
+    }
 }
 
 // ---------------------------------------------------------------- the verdict ----
@@ -330,6 +342,15 @@ inline int32_t stream_status(const xlz_zip_entry &x, int32_t status, uint64_t ou
 {
     if (status < 0) return status == XLZ_ERR_OUT_CAP && (x.flags & XLZ_ZIP_ENTRY_END_MARKER) ? (int32_t)XLZ_ERR_RESULT : status;
     return out_len == x.size ? (int32_t)XLZ_OK : (int32_t)XLZ_ERR_RESULT;
+}
+
+// What a deflate entry's item says of it: its own status where that is negative -- but XLZ_ERR_OUT_CAP, from a stream that only
+// wanted to go on behind the declared size: XLZ_ERR_RESULT, as for end-marker streams; XLZ_OK where it produced exactly the
+// entry's size; XLZ_ERR_RESULT otherwise.
+inline int32_t inflate_status(const xlz_zip_entry &x, int32_t status, uint64_t produced)
+{
+    if (status < 0) return status == XLZ_ERR_OUT_CAP ? (int32_t)XLZ_ERR_RESULT : status;
+    return produced == x.size ? (int32_t)XLZ_OK : (int32_t)XLZ_ERR_RESULT;
 }
 
 enum : uint8_t { kDigestGood = 0, kDigestBad = 1, kDigestNone = 2 }; // (none: verify is off)

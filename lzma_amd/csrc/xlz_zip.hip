@@ -6,7 +6,8 @@
 // gives the wanted method-14 entries to the batch engine through the tolerant device-destination stage
 // (xlz_internal_decode_device): one decode launch sequence, the CRC32 of every wanted entry on the device, one pack
 // into the windows, and the stored entries gathered into one pinned block, uploaded once and scattered by the pack kernel
-// (DeviceDest::gather_copies).
+// (DeviceDest::gather_copies).  In deflate mode 1 / 2 the wanted deflate entries are inflated in the same call
+// (DeviceDest::inflate: xlz_inflate_dev.hip, or host threads), in place, and checked where they lie.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -18,6 +19,10 @@
 #include "xlz_zip.h"
 
 using namespace xlzzip;
+
+// The context's deflate mode, as a WEAK reference: a program that is this file alone, without the library's contexts
+// (tests/c/zip_fuzz.cpp), links without it and is in mode 0.
+extern "C" int xlz_ctx_deflate_mode(const xlz_ctx *ctx) __attribute__((weak));
 
 static_assert(sizeof(xlz_zip_entry) == 72, "include/xlz.h documents the entry's size");
 static_assert(xlzzip::kDestStream == xlzpost::kDestStream, "xlz_zip.h names the destination as xlz_post.h does");
@@ -98,13 +103,16 @@ static int zip_extract(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_wan
         if (!device && wants[i].dst_cap >= x.size) dst[i] = staged, staged += x.size; // (no wrap: disjoint windows of out_cap hold them)
     }
     Plan p;
-    plan(a->file, e, wants, dst.data(), n, p);
+    const int deflate_mode = xlz_ctx_deflate_mode ? xlz_ctx_deflate_mode(ctx) : 0;
+    plan(a->file, e, wants, dst.data(), n, p, deflate_mode);
     const size_t ns = p.streams.size();
     xlz_zip_extract_stats xs = {};
     xs.entries = n, xs.lzma_entries = ns, xs.stored_entries = p.spans.size();
     for (size_t i = 0; i < n; i++) xs.empty_entries += !has_bytes(e[wants[i].entry]);
     for (size_t k = 0; k < ns; k++) xs.comp_bytes += e[wants[p.stream_want[k]].entry].comp_size;
     for (const Span &s : p.spans) xs.comp_bytes += s.len;
+    for (const xlz_inflate_item &it : p.inflate) xs.comp_bytes += it.in_len;
+    std::vector<xlz_inflate_result> ir(p.inflate.size());
     // (from here on the call has run: its statistics are published at its end, whatever the device then says)
     xlz_internal_check_stats_reset(ctx), xlz_internal_pack_stats_reset(ctx);
     std::vector<xlz_result> r(ns);
@@ -119,19 +127,22 @@ static int zip_extract(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_wan
     int st = XLZ_OK;
     void *staging = nullptr;
     if (!device && staged) st = xlz_internal_device_block(ctx, (size_t)staged, &staging);
-    if (st == XLZ_OK && (ns || !copies.empty())) {
+    if (st == XLZ_OK && (ns || !copies.empty() || !p.inflate.empty())) {
         const PostWork w = {nullptr, 0, cr.data(), cr.size(), got.data(), nullptr, true};
         DeviceDest dest;
         dest.d_dst = device ? d_out : staging, dest.cap = device ? out_cap : (size_t)staged;
         dest.want_out = want_out.data();
         dest.items = p.items.data(), dest.n_items = p.items.size(), dest.have_items = true, dest.tolerant = true;
         dest.copies = copies.data(), dest.n_copies = copies.size(), dest.gather_copies = true, dest.copy_uploads = &xs.stored_uploads;
+        dest.inflate = p.inflate.data(), dest.n_inflate = p.inflate.size(), dest.inflate_res = ir.data(), dest.inflate_mode = deflate_mode;
         st = xlz_internal_decode_device(ctx, p.streams.data(), ns, r.data(), w, dest);
     }
     // ---- the verdicts
     std::vector<int32_t> sst(n, XLZ_OK);
     std::vector<uint8_t> dig(n, kDigestNone);
     for (size_t k = 0; k < ns && st == XLZ_OK; k++) sst[p.stream_want[k]] = stream_status(e[wants[p.stream_want[k]].entry], r[k].status, r[k].out_len);
+    for (size_t k = 0; k < p.inflate.size() && st == XLZ_OK; k++)
+        sst[p.inflate_want[k]] = inflate_status(e[wants[p.inflate_want[k]].entry], ir[k].status, ir[k].produced);
     std::vector<xlz_zip_file_result> v(n);
     for (size_t i = 0; i < n && st == XLZ_OK; i++) {
         const xlz_zip_entry &x = e[wants[i].entry];
