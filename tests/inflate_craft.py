@@ -10,6 +10,11 @@ Tokens of a fixed or dynamic block:
     ("len", symbol, extra)   a length symbol and its extra bits, no distance behind it
     ("dist", symbol, extra)  a distance symbol and its extra bits (30, 31 in fixed blocks)
     ("bits", value, n)       n raw bits
+
+Bits.spans lists every field the writers wrote as (kind, first bit, bits) -- fields of no bits left out --, so that a test
+can say where in a field a given input bit lies.  The kinds: block-header (BFINAL and BTYPE), stored-pad, stored-len-nlen,
+stored-data; counts (HLIT, HDIST and HCLEN together), cl-length, cl-symbol, cl-extra-16 / -17 / -18; literal, length,
+length-extra, distance, distance-extra, end-of-block, bits.
 """
 
 LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
@@ -28,12 +33,16 @@ FLAT_CL = [4] * 13 + [5] * 6             # 19 symbols: 13 / 16 + 6 / 32 = 1
 
 
 class Bits:
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
+    """spans: [(kind, first bit, bits)] of every field written with a kind (fields of no bits are not listed)"""
 
-    def put(self, value, n):
+    def __init__(self):
+        self.acc, self.n, self.out, self.spans = 0, 0, bytearray(), []
+
+    def put(self, value, n, kind=None):
         """n bits of value, least significant first (header fields, extra bits)"""
         assert 0 <= value < (1 << n) or n == 0
+        if kind and n:
+            self.spans.append((kind, self.bit_len, n))
         self.acc |= value << self.n
         self.n += n
         while self.n >= 8:
@@ -41,13 +50,13 @@ class Bits:
             self.acc >>= 8
             self.n -= 8
 
-    def code(self, code, n):
+    def code(self, code, n, kind=None):
         """a Huffman code: most significant bit first"""
-        self.put(int(format(code, "0%db" % n)[::-1], 2) if n else 0, n)
+        self.put(int(format(code, "0%db" % n)[::-1], 2) if n else 0, n, kind)
 
-    def align(self):
+    def align(self, kind=None):
         if self.n:
-            self.put(0, 8 - self.n)
+            self.put(0, 8 - self.n, kind)
 
     @property
     def bit_len(self):
@@ -96,53 +105,57 @@ def dist_symbol(distance):
     return k, distance - DIST_BASE[k]
 
 
+def _lit_kind(symbol):
+    return "literal" if symbol < 256 else "end-of-block" if symbol == 256 else "length"
+
+
 def _emit(w, tokens, lit, dist):
     for t in tokens:
         if isinstance(t, int):
-            w.code(*lit[t])
+            w.code(*lit[t], kind="literal")
         elif t[0] == "m":
             length, distance = t[1], t[2]
             if len(t) > 3:
                 ls, lx = t[3], length - LEN_BASE[t[3] - 257]
             else:
                 ls, lx = len_symbol(length)
-            w.code(*lit[ls])
-            w.put(lx, LEN_EXTRA[ls - 257])
+            w.code(*lit[ls], kind="length")
+            w.put(lx, LEN_EXTRA[ls - 257], "length-extra")
             ds, dx = dist_symbol(distance)
-            w.code(*dist[ds])
-            w.put(dx, DIST_EXTRA[ds])
+            w.code(*dist[ds], kind="distance")
+            w.put(dx, DIST_EXTRA[ds], "distance-extra")
         elif t[0] == "lit":
-            w.code(*lit[t[1]])
+            w.code(*lit[t[1]], kind=_lit_kind(t[1]))
         elif t[0] == "len":
-            w.code(*lit[t[1]])
-            w.put(t[2], LEN_EXTRA[t[1] - 257])
+            w.code(*lit[t[1]], kind="length")
+            w.put(t[2], LEN_EXTRA[t[1] - 257], "length-extra")
         elif t[0] == "dist":
-            w.code(*dist[t[1]])
-            w.put(t[2], DIST_EXTRA[t[1]] if t[1] < 30 else 0)
+            w.code(*dist[t[1]], kind="distance")
+            w.put(t[2], DIST_EXTRA[t[1]] if t[1] < 30 else 0, "distance-extra")
         elif t[0] == "bits":
-            w.put(t[1], t[2])
+            w.put(t[1], t[2], "bits")
         else:
             raise ValueError(t)
 
 
 def stored(w, data, final=False, length=None, nlength=None):
     """a stored block; length / nlength override the two fields"""
-    w.put(1 if final else 0, 1)
-    w.put(0, 2)
-    w.align()
+    w.put(1 if final else 0, 3, "block-header")   # BFINAL, BTYPE 0
+    w.align("stored-pad")
     n = len(data) if length is None else length
-    w.put(n, 16)
-    w.put((n ^ 0xFFFF) if nlength is None else nlength, 16)
+    w.put(n | ((n ^ 0xFFFF) if nlength is None else nlength) << 16, 32, "stored-len-nlen")
+    at = w.bit_len
     for b in data:
         w.put(b, 8)
+    if data:
+        w.spans.append(("stored-data", at, 8 * len(data)))
 
 
 def fixed(w, tokens, final=False, eob=True):
-    w.put(1 if final else 0, 1)
-    w.put(1, 2)
+    w.put((1 if final else 0) | 1 << 1, 3, "block-header")
     _emit(w, tokens, canonical(FIXED_LIT), canonical(FIXED_DIST))
     if eob:
-        w.code(*canonical(FIXED_LIT)[256])
+        w.code(*canonical(FIXED_LIT)[256], kind="end-of-block")
 
 
 def plain_cl_seq(lengths):
@@ -157,8 +170,8 @@ def dynamic(w, tokens, lit_lens, dist_lens, final=False, eob=True, cl_lens=None,
     (symbol, extra) pairs that spell the lengths (default: one by one); body=False: the header alone"""
     cl_lens = list(FLAT_CL if cl_lens is None else cl_lens)
     cl_seq = plain_cl_seq(list(lit_lens) + list(dist_lens)) if cl_seq is None else cl_seq
-    w.put(1 if final else 0, 1)
-    w.put(2, 2)
+    w.put((1 if final else 0) | 2 << 1, 3, "block-header")
+    at = w.bit_len
     w.put(len(lit_lens) - 257 if hlit is None else hlit, 5)
     w.put(len(dist_lens) - 1 if hdist is None else hdist, 5)
     order = [cl_lens[s] for s in CL_ORDER]
@@ -167,23 +180,24 @@ def dynamic(w, tokens, lit_lens, dist_lens, final=False, eob=True, cl_lens=None,
         n -= 1
     n = n if hclen is None else hclen + 4
     w.put(n - 4, 4)
+    w.spans.append(("counts", at, 14))
     for l in order[:n]:
-        w.put(l, 3)
+        w.put(l, 3, "cl-length")
     cl = canonical(cl_lens)
     for s, x in cl_seq:
         if s in cl:
-            w.code(*cl[s])
+            w.code(*cl[s], kind="cl-symbol")
         else:
             assert not cl, "symbol %d has no code" % s
-            w.put(0, 1)  # (a code-length set without any code: a symbol is one bit)
+            w.put(0, 1, "cl-symbol")  # (a code-length set without any code: a symbol is one bit)
         if s >= 16:
-            w.put(x, {16: 2, 17: 3, 18: 7}[s])
+            w.put(x, {16: 2, 17: 3, 18: 7}[s], "cl-extra-%d" % s)
     if not body:
         return
     lit, dist = canonical(lit_lens), canonical(dist_lens)
     _emit(w, tokens, lit, dist)
     if eob:
-        w.code(*lit[256])
+        w.code(*lit[256], kind="end-of-block")
 
 
 def expand(tokens, start=b""):

@@ -302,10 +302,11 @@ def seeds():
     return out
 
 
-def mutations(n, seed):
-    """n (stream, out_cap) pairs: byte flips, cuts, spliced headers and changed room, of seeds()"""
+def mutations(n, seed, pool=None):
+    """n (stream, out_cap) pairs: byte flips, cuts, spliced headers and changed room, of seeds() -- or of `pool`, a list of
+    (good stream, its size)"""
     r = random.Random(seed)
-    pool = seeds()
+    pool = seeds() if pool is None else pool
     out = []
     while len(out) < n:
         data, size = pool[r.randrange(len(pool))]
