@@ -83,13 +83,17 @@ class Context:
             raise LzmaError(st, "xlz_ctx_batching_stats")
         return a.value, b.value
 
+    def _stats(self, struct, name):
+        """the context's `struct` as the library call `name` fills it in -> dict of its fields (but `reserved`)"""
+        s = struct()
+        st = getattr(N.lib(), name)(self._h, ctypes.byref(s))
+        if st != OK:
+            raise LzmaError(st, name)
+        return {k: getattr(s, k) for k, _ in struct._fields_ if k != "reserved"}
+
     def last_call_stats(self):
         """phase times and slot occupancy of the last decode_batch on this context (xlz_ctx_last_call_stats) -> dict"""
-        cs = N.CallStats()
-        st = N.lib().xlz_ctx_last_call_stats(self._h, ctypes.byref(cs))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_call_stats")
-        return {k: getattr(cs, k) for k, _ in N.CallStats._fields_}
+        return self._stats(N.CallStats, "xlz_ctx_last_call_stats")
 
     def set_slicing(self, min_call_bytes=0, slice_bytes=0, max_slices=0):
         """when a decode_batch of one wave round runs as a sequence of launches whose downloads overlap the decode
@@ -120,20 +124,12 @@ class Context:
     def last_check_stats(self):
         """who checked what in the last Batch.checks / decode_batch_checked / front-end call in check mode 1 on this
         context (xlz_ctx_last_check_stats) -> dict"""
-        cs = N.CheckStats()
-        st = N.lib().xlz_ctx_last_check_stats(self._h, ctypes.byref(cs))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_check_stats")
-        return {k: getattr(cs, k) for k, _ in N.CheckStats._fields_ if k != "reserved"}
+        return self._stats(N.CheckStats, "xlz_ctx_last_check_stats")
 
     def last_sha256_stats(self):
         """who hashed the SHA-256 ranges of the last Batch.digests / decode_batch_digests / xz_decode in check mode 2 on this
         context, and the threshold the plan chose (xlz_ctx_last_sha256_stats) -> dict"""
-        ss = N.Sha256Stats()
-        st = N.lib().xlz_ctx_last_sha256_stats(self._h, ctypes.byref(ss))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_sha256_stats")
-        return {k: getattr(ss, k) for k, _ in N.Sha256Stats._fields_ if k != "reserved"}
+        return self._stats(N.Sha256Stats, "xlz_ctx_last_sha256_stats")
 
     def set_filter_mode(self, mode):
         """what xz_decode / sevenzip_decode do with Delta / BCJ filter chains (xlz_ctx_set_filter_mode): 0 refuse them
@@ -151,40 +147,24 @@ class Context:
     def last_filter_stats(self):
         """what ran where in the last Batch.filter / decode_batch_filtered / front-end call in filter mode 1 on this context
         (xlz_ctx_last_filter_stats) -> dict"""
-        fs = N.FilterStats()
-        st = N.lib().xlz_ctx_last_filter_stats(self._h, ctypes.byref(fs))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_filter_stats")
-        return {k: getattr(fs, k) for k, _ in N.FilterStats._fields_ if k != "reserved"}
+        return self._stats(N.FilterStats, "xlz_ctx_last_filter_stats")
 
     def last_pack_stats(self):
         """what the pack kernel copied in the last Batch.pack / xz_decode_device / sevenzip_decode_device on this context
         (xlz_ctx_last_pack_stats) -> dict"""
-        ps = N.PackStats()
-        st = N.lib().xlz_ctx_last_pack_stats(self._h, ctypes.byref(ps))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_pack_stats")
-        return {k: getattr(ps, k) for k, _ in N.PackStats._fields_ if k != "reserved"}
+        return self._stats(N.PackStats, "xlz_ctx_last_pack_stats")
 
     def last_xz_read_stats(self):
         """what the last XzFile.read / read_ranges / read_device / read_tensor on this context decoded and copied
         (xlz_ctx_last_xz_read_stats) -> dict: blocks, comp_bytes and decoded_bytes are those of the covering blocks.  Such a
         read also leaves its *unverified -- covering blocks with a reserved check type -- in self.last_xz_unverified."""
-        rs = N.XzReadStats()
-        st = N.lib().xlz_ctx_last_xz_read_stats(self._h, ctypes.byref(rs))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_xz_read_stats")
-        return {k: getattr(rs, k) for k, _ in N.XzReadStats._fields_}
+        return self._stats(N.XzReadStats, "xlz_ctx_last_xz_read_stats")
 
     def last_xz_many_stats(self):
         """what the last xz_decode_many / xz_decode_many_into / xz_decode_many_device / xz_decode_many_tensor on this context
         was made of (xlz_ctx_last_xz_many_stats) -> dict: files and failed_files, the blocks and comp_bytes of the one batch,
         decoded_bytes = the sum over the good files"""
-        ms = N.XzManyStats()
-        st = N.lib().xlz_ctx_last_xz_many_stats(self._h, ctypes.byref(ms))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_xz_many_stats")
-        return {k: getattr(ms, k) for k, _ in N.XzManyStats._fields_}
+        return self._stats(N.XzManyStats, "xlz_ctx_last_xz_many_stats")
 
     def set_bcj2_mode(self, mode):
         """what sevenzip_decode / sevenzip_decode_device do with BCJ2 folders (xlz_ctx_set_bcj2_mode): 0 refuse them (default),
@@ -210,40 +190,24 @@ class Context:
         """what was inflated where in the last inflate_batch, or in the last ZipFile extraction in deflate mode 1 / 2 that had
         a deflate entry, on this context (xlz_ctx_last_inflate_stats) -> dict: device_items, device_bytes, host_items,
         host_bytes, failed_items, uploads, launches"""
-        s = N.InflateStats()
-        st = N.lib().xlz_ctx_last_inflate_stats(self._h, ctypes.byref(s))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_inflate_stats")
-        return {k: getattr(s, k) for k, _ in N.InflateStats._fields_}
+        return self._stats(N.InflateStats, "xlz_ctx_last_inflate_stats")
 
     def last_7z_extract_stats(self):
         """of the most recent SevenZipFile extraction on this context that ran: entries, empty_entries, failed_entries,
         folders, comp_bytes, decoded_bytes (what the batch was asked to decode), folder_bytes (the covering folders' full
         sizes: the difference is what the cuts saved), copied_bytes"""
-        s = N.SzExtractStats()
-        st = N.lib().xlz_ctx_last_7z_extract_stats(self._h, ctypes.byref(s))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_7z_extract_stats")
-        return {f: getattr(s, f) for f, _ in N.SzExtractStats._fields_}
+        return self._stats(N.SzExtractStats, "xlz_ctx_last_7z_extract_stats")
 
     def last_zip_extract_stats(self):
         """of the most recent ZipFile extraction on this context that ran: entries, empty_entries, failed_entries,
         lzma_entries (streams of the batch), stored_entries, comp_bytes, copied_bytes, stored_uploads (host-to-device
         transfers made for the stored entries: 1 however many there are, as long as they fit one staging block)"""
-        s = N.ZipExtractStats()
-        st = N.lib().xlz_ctx_last_zip_extract_stats(self._h, ctypes.byref(s))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_zip_extract_stats")
-        return {f: getattr(s, f) for f, _ in N.ZipExtractStats._fields_ if f != "reserved"}
+        return self._stats(N.ZipExtractStats, "xlz_ctx_last_zip_extract_stats")
 
     def last_tar_stats(self):
         """of the most recent tar_scan_device / TarXzFile.list on this context whose scan ran: blocks, zero_blocks,
         candidate_blocks (downloaded), header_blocks (reached by the walk), meta_bytes, downloaded_bytes, kernel_ms, launches"""
-        s = N.TarStats()
-        st = N.lib().xlz_ctx_last_tar_stats(self._h, ctypes.byref(s))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_tar_stats")
-        return {f: getattr(s, f) for f, _ in N.TarStats._fields_ if f != "reserved"}
+        return self._stats(N.TarStats, "xlz_ctx_last_tar_stats")
 
     def bcj2_mode(self):
         L = N.lib()
@@ -254,11 +218,7 @@ class Context:
     def last_bcj2_stats(self):
         """what merged where in the last Batch.bcj2 / sevenzip_decode / sevenzip_decode_device in bcj2 mode 1 / 2 on this
         context (xlz_ctx_last_bcj2_stats) -> dict"""
-        bs = N.Bcj2Stats()
-        st = N.lib().xlz_ctx_last_bcj2_stats(self._h, ctypes.byref(bs))
-        if st != OK:
-            raise LzmaError(st, "xlz_ctx_last_bcj2_stats")
-        return {k: getattr(bs, k) for k, _ in N.Bcj2Stats._fields_ if k != "reserved"}
+        return self._stats(N.Bcj2Stats, "xlz_ctx_last_bcj2_stats")
 
     def event_record(self, slot):
         st = N.lib().xlz_ctx_event_record(self._h, slot)
@@ -1163,7 +1123,9 @@ def sevenzip_decode_device(ctx, data, dptr, cap, verify=True):
     return _decode_device("xlz_7z_decode_device", ctx, data, dptr, cap, verify)
 
 
-def _decode_tensor(decode, total, ctx, data, verify, out):
+def _tensor_out(ctx, total, out, what):
+    """the tensor a *_tensor call writes: `out` if it is a contiguous one-dimensional torch.uint8 tensor of at least `total`
+    bytes on the context's device, a new one if it is None; `what` says who wants `total`, for the ERR_OUT_CAP text"""
     import torch  # (only here: importing lzma_amd does not import torch)
     dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
     if out is None:
@@ -1171,8 +1133,13 @@ def _decode_tensor(decode, total, ctx, data, verify, out):
     elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
         raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
     elif out.numel() < total:
-        raise LzmaError(ERR_OUT_CAP, "the index announces %d bytes, out holds %d" % (total, out.numel()))
+        raise LzmaError(ERR_OUT_CAP, "%s %d bytes, out holds %d" % (what, total, out.numel()))
     torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
+    return out
+
+
+def _decode_tensor(decode, total, ctx, data, verify, out):
+    out = _tensor_out(ctx, total, out, "the index announces")
     n = decode(ctx, data, out.data_ptr(), out.numel(), verify=verify)
     return out[:n]
 
@@ -1197,19 +1164,54 @@ class _PyBuffer(ctypes.Structure):  # Py_buffer of the C API: what PyObject_GetB
                 ("strides", ctypes.POINTER(ctypes.c_ssize_t)), ("suboffsets", ctypes.POINTER(ctypes.c_ssize_t)), ("internal", ctypes.c_void_p)]
 
 
-class XzFile:
+class _Borrowed:
+    """what XzFile, SevenZipFile and ZipFile are made on: `data` borrowed through the buffer protocol and the library's handle
+    over it, both held until close().  _name: the class as its messages call it; _close: the xlz_*_close of its handle"""
+    _name = _close = None
+
+    def _borrow(self, data):
+        self._h = ctypes.c_void_p()
+        self._view = _PyBuffer()
+        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:  # (raises: no buffer, not contiguous)
+            raise TypeError("%s needs bytes or a contiguous buffer" % self._name)
+        self._held = True
+
+    def _handle(self):
+        if not self._h:
+            raise LzmaError(ERR_CLOSED, "%s is closed" % self._name)
+        return self._h
+
+    def close(self):
+        if self._h:
+            getattr(N.lib(), self._close)(self._h)
+            self._h = ctypes.c_void_p()
+        if getattr(self, "_held", False):
+            self._held = False
+            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class XzFile(_Borrowed):
     """The parsed index of one .xz file (xlz_xz_open; host only): reads of byte ranges of the DECODED file decode the blocks
     that hold them and nothing else.  `data` is bytes or any contiguous buffer (bytearray, memoryview, mmap -- read-only
     ones too): it is borrowed through the buffer protocol, never copied, and held until close().  Raises LzmaError as
     xz_index_chains does.  Read-only once made: one XzFile may serve several threads and contexts.  A context manager;
     close() may be repeated."""
+    _name, _close = "XzFile", "xlz_xz_close"
 
     def __init__(self, data):
-        self._h = ctypes.c_void_p()
-        self._view = _PyBuffer()
-        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:  # (raises: no buffer, not contiguous)
-            raise TypeError("XzFile needs bytes or a contiguous buffer")
-        self._held = True
+        self._borrow(data)
         try:
             st = N.lib().xlz_xz_open(ctypes.c_void_p(self._view.buf), self._view.len, ctypes.byref(self._h))
             if st != OK:
@@ -1228,11 +1230,6 @@ class XzFile:
         fields = [f for f, _ in N.XzBlock._fields_]
         self.blocks = [{f: getattr(blocks[i], f) for f in fields} for i in range(nb.value)]
         self.steps = ns.value  # how many filter steps the blocks carry (xz_index_chains lists them)
-
-    def _handle(self):
-        if not self._h:
-            raise LzmaError(ERR_CLOSED, "XzFile is closed")
-        return self._h
 
     @staticmethod
     def _ranges(ranges):
@@ -1290,45 +1287,82 @@ class XzFile:
             return self.read_device(ctx, [(off, want, 0)], dptr, cap, verify=verify)[0]
         return _decode_tensor(read, want, ctx, None, verify, out)
 
-    def close(self):
-        if self._h:
-            N.lib().xlz_xz_close(self._h)
-            self._h = ctypes.c_void_p()
-        if getattr(self, "_held", False):
-            self._held = False
-            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- the files of a .7z archive (include/xlz.h: xlz_7z_open / xlz_7z_cover / xlz_7z_extract / xlz_7z_extract_device) ----
 SevenZipEntry = collections.namedtuple("SevenZipEntry", "name size is_dir has_stream crc mtime attributes folder folder_off is_anti")
 
 
-class SevenZipFile:
+class _EntryArchive(_Borrowed):
+    """what SevenZipFile and ZipFile share: an entry from its index or name, the windows of wanted entries, the three
+    forms of an extraction.  _prefix: of the C functions ("xlz_7z", "xlz_zip"); _Want / _Result: their structs; _row: the
+    fields of a result that make its tuple, status and out_len first"""
+    _prefix = _Want = _Result = _row = None
+
+    def index(self, which):
+        """an entry's index from an index or a name (the first entry of that name)"""
+        if isinstance(which, str):
+            try:
+                return self.names.index(which)
+            except ValueError:
+                raise KeyError(which)
+        return int(which)
+
+    def _list(self, which):
+        return [self.index(w) for w in ([which] if isinstance(which, (int, str)) else which)]
+
+    def _wants(self, wants):
+        arr = (self._Want * max(len(wants), 1))()
+        for i, w in enumerate(wants):
+            arr[i].entry, arr[i].dst_off, arr[i].dst_cap = int(w[0]), int(w[1]), int(w[2])
+        return arr
+
+    def layout(self, which, align=1):
+        idx = self._list(which)
+        arr = self._wants([(i, 0, 0) for i in idx])
+        total = ctypes.c_uint64()
+        name = self._prefix + "_extract_layout"
+        st = getattr(N.lib(), name)(self._handle(), arr, len(idx), int(align), ctypes.byref(total))
+        if st != OK:
+            raise LzmaError(st, name)
+        return [(arr[i].entry, arr[i].dst_off, arr[i].dst_cap) for i in range(len(idx))], total.value
+
+    def _extract(self, name, ctx, wants, dst, cap, verify):
+        res = (self._Result * max(len(wants), 1))()
+        st = getattr(N.lib(), name)(ctx._h if ctx is not None else None, self._handle(), self._wants(wants), len(wants), dst, int(cap),
+                                    1 if verify else 0, res)
+        if st != OK:
+            raise LzmaError(st, name)
+        return [tuple(getattr(res[i], f) for f in self._row) for i in range(len(wants))]
+
+    def extract_into(self, ctx, wants, out, verify=True):
+        dst = out if isinstance(out, ctypes.Array) else (ctypes.c_char * memoryview(out).nbytes).from_buffer(out)
+        return self._extract(self._prefix + "_extract", ctx, wants, ctypes.cast(dst, ctypes.c_void_p), ctypes.sizeof(dst), verify)
+
+    def extract_device(self, ctx, wants, dptr, cap, verify=True):
+        return self._extract(self._prefix + "_extract_device", ctx, wants, ctypes.c_void_p(int(dptr)), cap, verify)
+
+    def extract_tensor(self, ctx, which, verify=True, align=1, out=None):
+        """extract_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least the
+        layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(entry, off, out_len, status)]): an entry is
+        tensor[off:off + out_len] where its status is OK"""
+        wants, total = self.layout(which, align)
+        out = _tensor_out(ctx, total, out, "the layout needs")
+        res = self.extract_device(ctx, wants, out.data_ptr(), out.numel(), verify=verify)
+        return out, [(w[0], w[1], r[1], r[0]) for w, r in zip(wants, res)]
+
+
+class SevenZipFile(_EntryArchive):
     """The file table of one .7z archive (xlz_7z_open) and the extraction of chosen files as ONE batch: the folders that hold
     them, each decoded only as far as the last wanted file reaches.  `data` is bytes or any contiguous buffer; it is
     borrowed through the buffer protocol, never copied, and held until close().  ctx: needed only for an archive whose
     header is encoded (it is decoded on the device).  Raises LzmaError as sevenzip_index_bcj2 does, and for a FilesInfo
     section the parser refuses.  Names are AS STORED in the archive: do not trust one as a path.  Read-only once made; a
     context manager; close() may be repeated."""
+    _name, _close, _prefix = "SevenZipFile", "xlz_7z_close", "xlz_7z"
+    _Want, _Result, _row = N.SzWant, N.SzFileResult, ("status", "out_len", "unverified")
 
     def __init__(self, data, ctx=None):
-        self._h = ctypes.c_void_p()
-        self._view = _PyBuffer()
-        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:
-            raise TypeError("SevenZipFile needs bytes or a contiguous buffer")
-        self._held = True
+        self._borrow(data)
         try:
             L = N.lib()
             st = L.xlz_7z_open(ctx._h if ctx is not None else None, ctypes.c_void_p(self._view.buf), self._view.len, ctypes.byref(self._h))
@@ -1364,23 +1398,6 @@ class SevenZipFile:
         self.folders = [{f: getattr(fo[i], f) for f in fields} for i in range(nf.value)]
         self.names = [e.name for e in self.entries]
 
-    def _handle(self):
-        if not self._h:
-            raise LzmaError(ERR_CLOSED, "SevenZipFile is closed")
-        return self._h
-
-    def index(self, which):
-        """an entry's index from an index or a name (the first entry of that name)"""
-        if isinstance(which, str):
-            try:
-                return self.names.index(which)
-            except ValueError:
-                raise KeyError(which)
-        return int(which)
-
-    def _list(self, which):
-        return [self.index(w) for w in ([which] if isinstance(which, (int, str)) else which)]
-
     def cover(self, which):
         """xlz_7z_cover: [(folder, decode_len, in_len)] for the wanted entries (indices or names).  Host only."""
         idx = self._list(which)
@@ -1392,45 +1409,25 @@ class SevenZipFile:
             raise LzmaError(st, "xlz_7z_cover")
         return [(items[i].folder, items[i].decode_len, items[i].in_len) for i in range(n.value)]
 
-    def _wants(self, wants):
-        arr = (N.SzWant * max(len(wants), 1))()
-        for i, w in enumerate(wants):
-            arr[i].entry, arr[i].dst_off, arr[i].dst_cap = int(w[0]), int(w[1]), int(w[2])
-        return arr
-
     def layout(self, which, align=1):
         """xlz_7z_extract_layout: windows of the wanted entries back to back -> ([(entry, dst_off, dst_cap)], total)"""
-        idx = self._list(which)
-        arr = self._wants([(i, 0, 0) for i in idx])
-        total = ctypes.c_uint64()
-        st = N.lib().xlz_7z_extract_layout(self._handle(), arr, len(idx), int(align), ctypes.byref(total))
-        if st != OK:
-            raise LzmaError(st, "xlz_7z_extract_layout")
-        return [(arr[i].entry, arr[i].dst_off, arr[i].dst_cap) for i in range(len(idx))], total.value
-
-    def _extract(self, name, ctx, wants, dst, cap, verify):
-        res = (N.SzFileResult * max(len(wants), 1))()
-        st = getattr(N.lib(), name)(ctx._h, self._handle(), self._wants(wants), len(wants), dst, int(cap), 1 if verify else 0, res)
-        if st != OK:
-            raise LzmaError(st, name)
-        return [(res[i].status, res[i].out_len, res[i].unverified) for i in range(len(wants))]
+        return super().layout(which, align)
 
     def extract_into(self, ctx, wants, out, verify=True):
         """xlz_7z_extract with the caller's buffer: wants = [(entry, dst_off, dst_cap)] into `out` (a writable buffer); the
         windows of entries with bytes must not overlap -> [(status, out_len, unverified)]"""
-        dst = out if isinstance(out, ctypes.Array) else (ctypes.c_char * memoryview(out).nbytes).from_buffer(out)
-        return self._extract("xlz_7z_extract", ctx, wants, ctypes.cast(dst, ctypes.c_void_p), ctypes.sizeof(dst), verify)
+        return super().extract_into(ctx, wants, out, verify)
 
     def extract_device(self, ctx, wants, dptr, cap, verify=True):
         """xlz_7z_extract_device: the same into `cap` bytes of device memory at the address `dptr` (on the context's device)"""
-        return self._extract("xlz_7z_extract_device", ctx, wants, ctypes.c_void_p(int(dptr)), cap, verify)
+        return super().extract_device(ctx, wants, dptr, cap, verify)
 
     def extract(self, ctx, which, verify=True):
         """the wanted entries (indices or names) as ONE batch -> a list with bytes, or an LzmaError INSTANCE, per entry; only
         what concerns the whole call is raised"""
         wants, total = self.layout(which)
         out = ctypes.create_string_buffer(max(total, 1))
-        res = self._extract("xlz_7z_extract", ctx, wants, ctypes.cast(out, ctypes.c_void_p), total, verify)
+        res = self._extract(self._prefix + "_extract", ctx, wants, ctypes.cast(out, ctypes.c_void_p), total, verify)
         base = ctypes.addressof(out)
         return [ctypes.string_at(base + w[1], n) if st == OK else LzmaError(st, "xlz_7z_extract: entry %d" % w[0])
                 for w, (st, n, _) in zip(wants, res)]
@@ -1442,46 +1439,9 @@ class SevenZipFile:
             raise got
         return got
 
-    def extract_tensor(self, ctx, which, verify=True, align=1, out=None):
-        """extract_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least the
-        layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(entry, off, out_len, status)]): an entry is
-        tensor[off:off + out_len] where its status is OK"""
-        import torch  # (only here: importing lzma_amd does not import torch)
-        dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
-        wants, total = self.layout(which, align)
-        if out is None:
-            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
-            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
-        elif out.numel() < total:
-            raise LzmaError(ERR_OUT_CAP, "the layout needs %d bytes, out holds %d" % (total, out.numel()))
-        torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
-        res = self.extract_device(ctx, wants, out.data_ptr(), out.numel(), verify=verify)
-        return out, [(w[0], w[1], n, st) for w, (st, n, _) in zip(wants, res)]
-
-    def close(self):
-        if self._h:
-            N.lib().xlz_7z_close(self._h)
-            self._h = ctypes.c_void_p()
-        if getattr(self, "_held", False):
-            self._held = False
-            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- the entries of a .zip archive (include/xlz.h: xlz_zip_open / xlz_zip_extract / xlz_zip_extract_device) ----
-class ZipFile:
+class ZipFile(_EntryArchive):
     """The table of one .zip archive (xlz_zip_open; host only) and the extraction of chosen entries as ONE batch: every
     wanted method-14 (LZMA) entry is a stream of one decode launch sequence, stored entries go up in one transfer, the
     CRC32 of every entry is checked on the device.  `data` is bytes or any contiguous buffer; it is borrowed through the
@@ -1492,13 +1452,11 @@ class ZipFile:
     context's deflate mode 1 / 2, refused in mode 0; `supported` is false for it as ever); .names: decoded as zipfile does, UTF-8 where flag bit 11
     is set, else CP437.  Names are AS STORED in the archive: do not trust one as a path.  Read-only once made; a context
     manager; close() may be repeated."""
+    _name, _close, _prefix = "ZipFile", "xlz_zip_close", "xlz_zip"
+    _Want, _Result, _row = N.ZipWant, N.ZipFileResult, ("status", "out_len")
 
     def __init__(self, data):
-        self._h = ctypes.c_void_p()
-        self._view = _PyBuffer()
-        if ctypes.pythonapi.PyObject_GetBuffer(ctypes.py_object(data), ctypes.byref(self._view), 0) != 0:
-            raise TypeError("ZipFile needs bytes or a contiguous buffer")
-        self._held = True
+        self._borrow(data)
         try:
             L = N.lib()
             st = L.xlz_zip_open(ctypes.c_void_p(self._view.buf), self._view.len, ctypes.byref(self._h))
@@ -1532,63 +1490,25 @@ class ZipFile:
             self.entries.append(d)
         self.names = [e["name"] for e in self.entries]
 
-    def _handle(self):
-        if not self._h:
-            raise LzmaError(ERR_CLOSED, "ZipFile is closed")
-        return self._h
-
-    def index(self, which):
-        """an entry's index from an index or a name (the first entry of that name)"""
-        if isinstance(which, str):
-            try:
-                return self.names.index(which)
-            except ValueError:
-                raise KeyError(which)
-        return int(which)
-
-    def _list(self, which):
-        return [self.index(w) for w in ([which] if isinstance(which, (int, str)) else which)]
-
-    def _wants(self, wants):
-        arr = (N.ZipWant * max(len(wants), 1))()
-        for i, w in enumerate(wants):
-            arr[i].entry, arr[i].dst_off, arr[i].dst_cap = int(w[0]), int(w[1]), int(w[2])
-        return arr
-
     def layout(self, which, align=1):
         """xlz_zip_extract_layout: windows of the wanted entries back to back -> ([(entry, dst_off, dst_cap)], total)"""
-        idx = self._list(which)
-        arr = self._wants([(i, 0, 0) for i in idx])
-        total = ctypes.c_uint64()
-        st = N.lib().xlz_zip_extract_layout(self._handle(), arr, len(idx), int(align), ctypes.byref(total))
-        if st != OK:
-            raise LzmaError(st, "xlz_zip_extract_layout")
-        return [(arr[i].entry, arr[i].dst_off, arr[i].dst_cap) for i in range(len(idx))], total.value
-
-    def _extract(self, name, ctx, wants, dst, cap, verify):
-        res = (N.ZipFileResult * max(len(wants), 1))()
-        st = getattr(N.lib(), name)(ctx._h if ctx is not None else None, self._handle(), self._wants(wants), len(wants), dst, int(cap),
-                                    1 if verify else 0, res)
-        if st != OK:
-            raise LzmaError(st, name)
-        return [(res[i].status, res[i].out_len) for i in range(len(wants))]
+        return super().layout(which, align)
 
     def extract_into(self, ctx, wants, out, verify=True):
         """xlz_zip_extract with the caller's buffer: wants = [(entry, dst_off, dst_cap)] into `out` (a writable buffer); the
         windows of entries with bytes must not overlap -> [(status, out_len)]"""
-        dst = out if isinstance(out, ctypes.Array) else (ctypes.c_char * memoryview(out).nbytes).from_buffer(out)
-        return self._extract("xlz_zip_extract", ctx, wants, ctypes.cast(dst, ctypes.c_void_p), ctypes.sizeof(dst), verify)
+        return super().extract_into(ctx, wants, out, verify)
 
     def extract_device(self, ctx, wants, dptr, cap, verify=True):
         """xlz_zip_extract_device: the same into `cap` bytes of device memory at the address `dptr` (on the context's device)"""
-        return self._extract("xlz_zip_extract_device", ctx, wants, ctypes.c_void_p(int(dptr)), cap, verify)
+        return super().extract_device(ctx, wants, dptr, cap, verify)
 
     def extract(self, ctx, which, verify=True):
         """the wanted entries (indices or names) as ONE batch -> [(status, bytes)], bytes empty unless the status is OK; only
         what concerns the whole call is raised"""
         wants, total = self.layout(which)
         out = ctypes.create_string_buffer(max(total, 1))
-        res = self._extract("xlz_zip_extract", ctx, wants, ctypes.cast(out, ctypes.c_void_p), total, verify)
+        res = self._extract(self._prefix + "_extract", ctx, wants, ctypes.cast(out, ctypes.c_void_p), total, verify)
         base = ctypes.addressof(out)
         return [(st, ctypes.string_at(base + w[1], n) if st == OK else b"") for w, (st, n) in zip(wants, res)]
 
@@ -1599,43 +1519,6 @@ class ZipFile:
         if st != OK:
             raise LzmaError(st, "xlz_zip_extract: entry %d" % i)
         return got
-
-    def extract_tensor(self, ctx, which, verify=True, align=1, out=None):
-        """extract_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least the
-        layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(entry, off, out_len, status)]): an entry is
-        tensor[off:off + out_len] where its status is OK"""
-        import torch  # (only here: importing lzma_amd does not import torch)
-        dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
-        wants, total = self.layout(which, align)
-        if out is None:
-            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
-            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
-        elif out.numel() < total:
-            raise LzmaError(ERR_OUT_CAP, "the layout needs %d bytes, out holds %d" % (total, out.numel()))
-        torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
-        res = self.extract_device(ctx, wants, out.data_ptr(), out.numel(), verify=verify)
-        return out, [(w[0], w[1], n, st) for w, (st, n) in zip(wants, res)]
-
-    def close(self):
-        if self._h:
-            N.lib().xlz_zip_close(self._h)
-            self._h = ctypes.c_void_p()
-        if getattr(self, "_held", False):
-            self._held = False
-            ctypes.pythonapi.PyBuffer_Release(ctypes.byref(self._view))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- the members of a .tar image (include/xlz.h: xlz_tar_parse_host / xlz_tar_scan_device / xlz_xz_tar_list) ----
@@ -1861,16 +1744,7 @@ def xz_decode_many_tensor(ctx, datas, verify=True, align=1, out=None):
     """xz_decode_many_device into a torch.uint8 tensor on the context's device: `out` (one-dimensional, contiguous, at least
     the layout's total; ERR_OUT_CAP if smaller) or a new one -> (tensor, [(off, out_len, status, unverified)]): file i is
     tensor[off:off + out_len] where its status is OK"""
-    import torch  # (only here: importing lzma_amd does not import torch)
-    dev = torch.device("cuda", N.lib().xlz_ctx_device(ctx._h))
     with _ManyFiles(datas) as m:
-        total = m.layout(_chains_of(None, ctx), align)
-        if out is None:
-            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.dim() == 1 and out.is_contiguous()):
-            raise ValueError("out must be a contiguous one-dimensional torch.uint8 tensor on %s" % dev)
-        elif out.numel() < total:
-            raise LzmaError(ERR_OUT_CAP, "the indexes announce %d bytes, out holds %d" % (total, out.numel()))
-        torch.cuda.synchronize(dev)  # (torch's pending work on the tensor; the library works on a stream of its own and waits for it)
+        out = _tensor_out(ctx, m.layout(_chains_of(None, ctx), align), out, "the indexes announce")
         res = m.decode("xlz_xz_decode_many_device", ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), verify)
         return out, [(m.arr[i].dst_off, n, st, nu) for i, (st, n, nu) in enumerate(res)]

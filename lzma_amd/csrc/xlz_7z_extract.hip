@@ -106,13 +106,13 @@ static int sz_extract(xlz_ctx *ctx, const xlz_7z_archive *a, const xlz_7z_want *
     const size_t nf = a->folders.size();
     std::vector<uint8_t> touched(nf, 0);
     std::vector<uint64_t> dst(n, 0);
-    uint64_t staged = 0; // host form: the staging block's size
+    HostStaging staging(ctx); // host form: the wanted sizes back to back
     for (size_t i = 0; i < n; i++) {
         const xlz_7z_entry &x = e[wants[i].entry];
         if (!has_bytes(x)) continue;
         touched[(size_t)x.folder] = 1;
         dst[i] = wants[i].dst_off;
-        if (!device && wants[i].dst_cap >= x.size) dst[i] = staged, staged += x.size; // (no wrap: disjoint windows of out_cap hold them)
+        if (!device && wants[i].dst_cap >= x.size) dst[i] = staging.add(x.size);
     }
     Shapes sh;
     shapes(a, touched, xlz_ctx_filter_mode(ctx) == 1, sh);
@@ -173,13 +173,11 @@ static int sz_extract(xlz_ctx *ctx, const xlz_7z_archive *a, const xlz_7z_want *
         else
             copies.push_back(DeviceCopy{dst[p.copy_wants[j]], a->file + f.pack_off + x.folder_off, x.size});
     }
-    int st = XLZ_OK;
-    void *staging = nullptr;
-    if (!device && staged) st = xlz_internal_device_block(ctx, (size_t)staged, &staging);
+    int st = staging.acquire();
     if (st == XLZ_OK && (ns || !copies.empty())) {
         const PostWork w = {fs.data(), fs.size(), cr.data(), cr.size(), got.data(), nullptr, true};
         DeviceDest dest;
-        dest.d_dst = device ? d_out : staging, dest.cap = device ? out_cap : (size_t)staged;
+        dest.d_dst = device ? d_out : staging.d_dst(), dest.cap = device ? out_cap : staging.cap();
         dest.want_out = want_out.data(), dest.want_in = want_in.data(), dest.want_status = want_status.data();
         dest.items = p.items.data(), dest.n_items = p.items.size(), dest.have_items = true, dest.tolerant = true;
         dest.copies = copies.data(), dest.n_copies = copies.size();
@@ -208,17 +206,7 @@ static int sz_extract(xlz_ctx *ctx, const xlz_7z_archive *a, const xlz_7z_want *
     if (host_ranges) xlz_internal_check_stats_host(ctx, host_ranges, host_bytes);
     std::vector<xlz_7z_file_result> v(n);
     for (size_t i = 0; i < n && st == XLZ_OK; i++) v[i] = verdict(p.pre[i], e[wants[i].entry], fst[i], dig[i], verify != 0);
-    if (st == XLZ_OK && staging) { // ONE copy of the staging block, the good entries scattered on the host
-        std::vector<uint8_t> bounce((size_t)staged);
-        st = xlz_internal_device_block_download(ctx, staging, bounce.data(), bounce.size());
-        for (size_t i = 0; i < n && st == XLZ_OK; i++)
-            if (v[i].status == XLZ_OK && v[i].out_len) memcpy(out + wants[i].dst_off, bounce.data() + dst[i], (size_t)v[i].out_len);
-    }
-    if (staging) xlz_internal_device_block_release(ctx, staging);
-    for (size_t i = 0; i < n; i++) {
-        results[i] = st == XLZ_OK ? v[i] : xlz_7z_file_result{st, 0, 0};
-        xs.failed_entries += results[i].status != XLZ_OK, xs.copied_bytes += results[i].out_len;
-    }
+    st = xlz_internal_extract_finish(staging, st, wants, dst.data(), v, out, results, xs); // (ONE copy of the staging block, the good entries scattered)
     xlz_internal_7z_extract_stats_set(ctx, xs);
     return st;
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/xlz.h"
+#include "xlz_windows.h"
 
 namespace xlz7zf {
 
@@ -323,36 +324,22 @@ inline int32_t expected_status(uint8_t kind) { return kind == kWhole ? (int32_t)
 // one with dst_cap == 0, declares no byte, wherever its dst_off points.
 inline bool wants_ok(const xlz_7z_entry *e, size_t ne, const xlz_7z_want *w, size_t n, uint64_t out_cap)
 {
-    std::vector<std::pair<uint64_t, uint64_t>> win;
+    std::vector<xlzwin::Window> win;
     for (size_t i = 0; i < n; i++) {
         if (w[i].entry >= ne) return false;
-        if (!has_bytes(e[w[i].entry]) || !w[i].dst_cap) continue;
-        if (w[i].dst_off > out_cap || w[i].dst_cap > out_cap - w[i].dst_off) return false;
-        win.emplace_back(w[i].dst_off, w[i].dst_off + w[i].dst_cap);
+        if (has_bytes(e[w[i].entry]) && w[i].dst_cap) win.emplace_back(w[i].dst_off, w[i].dst_cap);
     }
-    std::sort(win.begin(), win.end());
-    for (size_t i = 1; i < win.size(); i++)
-        if (win[i - 1].second > win[i].first) return false;
-    return true;
+    return xlzwin::disjoint_within(std::move(win), out_cap);
 }
 
 // Windows of the wanted entries' sizes back to back, in order: dst_off = the first multiple of align (>= 1) at or behind
 // the end of the window before, *total = the end of the last one.  false: an offset or an end does not fit 64 bits.
 inline bool layout(const xlz_7z_entry *e, xlz_7z_want *w, size_t n, uint64_t align, uint64_t *total)
 {
-    const uint64_t top = ~(uint64_t)0;
-    uint64_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t over = at % align, size = e[w[i].entry].size;
-        if (over) {
-            if (align - over > top - at) return false;
-            at += align - over;
-        }
-        if (size > top - at) return false;
-        w[i].dst_off = at, w[i].dst_cap = size;
-        at += size;
-    }
-    *total = at;
+    std::vector<uint64_t> size(n), off(n);
+    for (size_t i = 0; i < n; i++) size[i] = e[w[i].entry].size;
+    if (!xlzwin::back_to_back(size.data(), n, align, off.data(), total)) return false;
+    for (size_t i = 0; i < n; i++) w[i].dst_off = off[i], w[i].dst_cap = size[i];
     return true;
 }
 

@@ -1,6 +1,9 @@
 // xlz_check_host.h -- what the container front-ends (xlz_xz.hip, xlz_7z.hip) use of the post-decode stage in
 // xlz_host.hip.  Not part of the C ABI.
 #pragma once
+#include <cstring>
+#include <vector>
+
 #include "../../include/xlz.h"
 #include "xlz_post.h"
 
@@ -89,6 +92,67 @@ struct DeviceDest {
 int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p);
 int xlz_internal_device_block_download(xlz_ctx *ctx, const void *p, uint8_t *dst, size_t bytes);
 void xlz_internal_device_block_release(xlz_ctx *ctx, void *p);
+// The host form of a device-destination call (xlz_xz_read, xlz_7z_extract, xlz_zip_extract): what the call wants lies back
+// to back in ONE such block -- add() while planning, acquire() (no block where nothing was added), d_dst() / cap() for
+// DeviceDest --, comes down in one copy and is scattered on the host.  The block goes back behind the download, and
+// at the latest when the object goes.
+class HostStaging {
+public:
+    struct Piece { // block bytes [staged, staged + len) -> out + dst_off
+        uint64_t staged, dst_off, len;
+    };
+    explicit HostStaging(xlz_ctx *ctx) : ctx_(ctx) {}
+    HostStaging(const HostStaging &) = delete;
+    HostStaging &operator=(const HostStaging &) = delete;
+    ~HostStaging() { xlz_internal_device_block_release(ctx_, block_); }
+    uint64_t add(uint64_t len) // -> where these bytes lie in the block (no wrap: disjoint windows of a size_t capacity hold them)
+    {
+        size_ += len;
+        return size_ - len;
+    }
+    int acquire() { return size_ ? xlz_internal_device_block(ctx_, (size_t)size_, &block_) : (int)XLZ_OK; }
+    void *d_dst() const { return block_; }
+    size_t cap() const { return (size_t)size_; }
+    // ONE copy of the block: straight into `out` where one piece is all of it, else through a bounce buffer
+    int download(uint8_t *out, const std::vector<Piece> &pieces)
+    {
+        int st = XLZ_OK;
+        if (pieces.size() == 1 && pieces[0].staged == 0 && pieces[0].len == size_)
+            st = xlz_internal_device_block_download(ctx_, block_, out + pieces[0].dst_off, (size_t)size_);
+        else if (!pieces.empty()) {
+            std::vector<uint8_t> bounce((size_t)size_);
+            st = xlz_internal_device_block_download(ctx_, block_, bounce.data(), bounce.size());
+            for (size_t j = 0; j < pieces.size() && st == XLZ_OK; j++) memcpy(out + pieces[j].dst_off, bounce.data() + pieces[j].staged, (size_t)pieces[j].len);
+        }
+        xlz_internal_device_block_release(ctx_, block_);
+        block_ = nullptr;
+        return st;
+    }
+
+private:
+    xlz_ctx *ctx_;
+    uint64_t size_ = 0;
+    void *block_ = nullptr;
+};
+// The end of xlz_7z_extract / xlz_zip_extract: st = what the batch said; v[i] = want i's verdict, whose bytes -- where it is
+// XLZ_OK -- lie at dst[i] of the staging block (if there is one) and go to out + wants[i].dst_off.  results[] = the
+// verdicts, or the call's failure for every want; xs counts the failed and the copied.  -> the call's status
+template <class Want, class Result, class Stats>
+int xlz_internal_extract_finish(HostStaging &staging, int st, const Want *wants, const uint64_t *dst, const std::vector<Result> &v, uint8_t *out,
+                                Result *results, Stats &xs)
+{
+    if (st == XLZ_OK && staging.d_dst()) {
+        std::vector<HostStaging::Piece> good;
+        for (size_t i = 0; i < v.size(); i++)
+            if (v[i].status == XLZ_OK && v[i].out_len) good.push_back({dst[i], wants[i].dst_off, v[i].out_len});
+        st = staging.download(out, good);
+    }
+    for (size_t i = 0; i < v.size(); i++) {
+        results[i] = st == XLZ_OK ? v[i] : Result{st, 0, 0};
+        xs.failed_entries += results[i].status != XLZ_OK, xs.copied_bytes += results[i].out_len;
+    }
+    return st;
+}
 // XLZ_OK: [p, p + cap) is device memory of the context's device, as far as the runtime tells (what xlz_batch_pack asks of d_dst)
 int xlz_internal_device_dst_ok(xlz_ctx *ctx, const void *p, size_t cap);
 void xlz_internal_bcj2_stats_reset(xlz_ctx *ctx);

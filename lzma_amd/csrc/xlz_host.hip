@@ -1908,14 +1908,18 @@ void sha256_host_jobs(const std::vector<ShaHostJob> &jobs)
 }
 void sha256_of_nothing(xlz_digest *out) { xlzcheck::sha256(out->b, 0, out->b); }
 
-// the statistics of a finished call become the context's: `tag` is what xlzpost::stats_add wants behind its two operands
-template <class T, class... Tag> void publish(xlz_ctx *ctx, T xlz_ctx::*member, const T &v, bool accumulate, Tag... tag)
+// the statistics of a finished call become the context's ...
+template <class T> void publish(xlz_ctx *ctx, T xlz_ctx::*member, const T &v)
 {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (accumulate)
-        xlzpost::stats_add(ctx->*member, v, tag...);
-    else
-        ctx->*member = v;
+    ctx->*member = v;
+}
+// ... or, with accumulate, add to them: `tag` is what xlzpost::stats_add wants behind its two operands
+template <class T, class... Tag> void publish(xlz_ctx *ctx, T xlz_ctx::*member, const T &v, bool accumulate, Tag... tag)
+{
+    if (!accumulate) return publish(ctx, member, v);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    xlzpost::stats_add(ctx->*member, v, tag...);
 }
 // ... and are read: xlz_ctx_last_check_stats, xlz_ctx_last_sha256_stats, xlz_ctx_last_filter_stats
 template <class T> int last_stats(xlz_ctx *ctx, T xlz_ctx::*member, T *out)
@@ -1923,6 +1927,14 @@ template <class T> int last_stats(xlz_ctx *ctx, T xlz_ctx::*member, T *out)
     if (!ctx || !out) return XLZ_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     *out = ctx->*member;
+    return XLZ_OK;
+}
+// ... and a mode 0 .. top is set: xlz_ctx_set_check_mode, xlz_ctx_set_filter_mode, xlz_ctx_set_bcj2_mode, xlz_ctx_set_deflate_mode
+int set_mode(xlz_ctx *ctx, int xlz_ctx::*member, int mode, int top)
+{
+    if (!ctx || mode < 0 || mode > top) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->*member = mode;
     return XLZ_OK;
 }
 
@@ -2145,13 +2157,7 @@ extern "C" uint32_t xlz_crc32_combine(uint32_t a, uint32_t b, uint64_t len_b)
 }
 extern "C" uint64_t xlz_crc64_combine(uint64_t a, uint64_t b, uint64_t len_b) { return xlzchk::combine<64>(check_host().c64, a, b, len_b); }
 
-extern "C" int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode)
-{
-    if (!ctx || (mode != 0 && mode != 1 && mode != 2)) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->check_mode = mode;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_set_check_mode(xlz_ctx *ctx, int mode) { return set_mode(ctx, &xlz_ctx::check_mode, mode, 2); }
 extern "C" int xlz_ctx_check_mode(const xlz_ctx *ctx) { return ctx ? ctx->check_mode : XLZ_ERR_BAD_ARG; }
 
 extern "C" int xlz_ctx_last_check_stats(xlz_ctx *ctx, xlz_check_stats *out) { return last_stats(ctx, &xlz_ctx::last_check, out); }
@@ -2303,13 +2309,7 @@ extern "C" int xlz_batch_filter(xlz_batch *b, const xlz_filter_step *steps, size
     return st;
 }
 
-extern "C" int xlz_ctx_set_filter_mode(xlz_ctx *ctx, int mode)
-{
-    if (!ctx || (mode != 0 && mode != 1)) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->filter_mode = mode;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_set_filter_mode(xlz_ctx *ctx, int mode) { return set_mode(ctx, &xlz_ctx::filter_mode, mode, 1); }
 extern "C" int xlz_ctx_filter_mode(const xlz_ctx *ctx) { return ctx ? ctx->filter_mode : XLZ_ERR_BAD_ARG; }
 
 extern "C" int xlz_ctx_last_filter_stats(xlz_ctx *ctx, xlz_filter_stats *out) { return last_stats(ctx, &xlz_ctx::last_filter, out); }
@@ -2422,32 +2422,16 @@ void xlz_internal_pack_stats_reset(xlz_ctx *ctx) { publish(ctx, &xlz_ctx::last_p
 
 // byte ranges of an .xz file (xlz_xz.hip: xlz_xz_read / xlz_xz_read_device)
 extern "C" int xlz_ctx_last_xz_read_stats(xlz_ctx *ctx, xlz_xz_read_stats *out) { return last_stats(ctx, &xlz_ctx::last_xz_read, out); }
-void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_xz_read = s;
-}
+void xlz_internal_xz_read_stats_set(xlz_ctx *ctx, const xlz_xz_read_stats &s) { publish(ctx, &xlz_ctx::last_xz_read, s); }
 // many .xz files as one batch (xlz_xz.hip: xlz_xz_decode_many / xlz_xz_decode_many_device)
 extern "C" int xlz_ctx_last_xz_many_stats(xlz_ctx *ctx, xlz_xz_many_stats *out) { return last_stats(ctx, &xlz_ctx::last_xz_many, out); }
-void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_xz_many = s;
-}
+void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s) { publish(ctx, &xlz_ctx::last_xz_many, s); }
 // chosen files of a .7z archive (xlz_7z_extract.hip: xlz_7z_extract / xlz_7z_extract_device)
 extern "C" int xlz_ctx_last_7z_extract_stats(xlz_ctx *ctx, xlz_7z_extract_stats *out) { return last_stats(ctx, &xlz_ctx::last_7z_extract, out); }
-void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_7z_extract = s;
-}
+void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s) { publish(ctx, &xlz_ctx::last_7z_extract, s); }
 // chosen entries of a .zip archive (xlz_zip.hip: xlz_zip_extract / xlz_zip_extract_device)
 extern "C" int xlz_ctx_last_zip_extract_stats(xlz_ctx *ctx, xlz_zip_extract_stats *out) { return last_stats(ctx, &xlz_ctx::last_zip_extract, out); }
-void xlz_internal_zip_extract_stats_set(xlz_ctx *ctx, const xlz_zip_extract_stats &s)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_zip_extract = s;
-}
+void xlz_internal_zip_extract_stats_set(xlz_ctx *ctx, const xlz_zip_extract_stats &s) { publish(ctx, &xlz_ctx::last_zip_extract, s); }
 
 namespace {
 
@@ -2595,11 +2579,7 @@ int xlz_internal_tar_gather_device(xlz_ctx *ctx, const void *d_image, uint64_t l
         out_host, d_stage, n * 512, ms);
 }
 extern "C" int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *out) { return last_stats(ctx, &xlz_ctx::last_tar, out); }
-void xlz_internal_tar_stats_set(xlz_ctx *ctx, const xlz_tar_stats &s)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_tar = s;
-}
+void xlz_internal_tar_stats_set(xlz_ctx *ctx, const xlz_tar_stats &s) { publish(ctx, &xlz_ctx::last_tar, s); }
 
 // ---------------------------------------------------------------- BCJ2 folders ----
 namespace xlz {
@@ -2614,18 +2594,15 @@ static_assert(kOutTailPad >= 16 && kArenaAlign % 16 == 0, "xlz_bcj2_dev.h reads 
 // xlz_batch_bcj2's table as the caller declares it (cf. xlzpost::pack_items_ok)
 bool bcj2_items_ok(const xlz_bcj2_item *items, size_t n, size_t n_streams, uint64_t dst_cap)
 {
-    std::vector<std::pair<uint64_t, uint64_t>> r;
+    std::vector<xlzwin::Window> r;
     for (size_t i = 0; i < n; i++) {
         const xlz_bcj2_item &it = items[i];
         for (const xlz_bcj2_src *s : {&it.main_s, &it.call_s, &it.jump_s})
             if (s->stream == XLZ_BCJ2_RAW ? (!s->raw && s->raw_len) : s->stream >= n_streams) return false;
-        if ((!it.rc && it.rc_len) || it.dst_off > dst_cap || it.out_len > dst_cap - it.dst_off) return false;
-        if (it.out_len) r.emplace_back(it.dst_off, it.dst_off + it.out_len);
+        if (!it.rc && it.rc_len) return false;
+        r.emplace_back(it.dst_off, it.out_len);
     }
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); i++)
-        if (r[i - 1].second > r[i].first) return false;
-    return true;
+    return xlzwin::disjoint_within(std::move(r), dst_cap);
 }
 
 // one of an item's four streams, resolved against a collected batch
@@ -2796,13 +2773,7 @@ extern "C" int xlz_batch_bcj2(xlz_batch *b, const xlz_bcj2_item *items, size_t n
     return st;
 }
 
-extern "C" int xlz_ctx_set_bcj2_mode(xlz_ctx *ctx, int mode)
-{
-    if (!ctx || mode < 0 || mode > 2) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->bcj2_mode = mode;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_set_bcj2_mode(xlz_ctx *ctx, int mode) { return set_mode(ctx, &xlz_ctx::bcj2_mode, mode, 2); }
 extern "C" int xlz_ctx_bcj2_mode(const xlz_ctx *ctx) { return ctx ? ctx->bcj2_mode : XLZ_ERR_BAD_ARG; }
 extern "C" int xlz_ctx_last_bcj2_stats(xlz_ctx *ctx, xlz_bcj2_stats *out) { return last_stats(ctx, &xlz_ctx::last_bcj2, out); }
 
@@ -2820,26 +2791,15 @@ static_assert(xlzinf::kStOk == XLZ_OK && xlzinf::kStResult == XLZ_ERR_RESULT && 
                   xlzinf::kStOutCap == XLZ_ERR_OUT_CAP,
               "xlz_inflate_dev.h names the statuses of include/xlz.h");
 
-void inflate_stats_set(xlz_ctx *ctx, const xlz_inflate_stats &s)
-{
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->last_inflate = s;
-}
-
 // xlz_inflate_batch's table as the caller declares it (cf. bcj2_items_ok)
 bool inflate_items_ok(const xlz_inflate_item *items, size_t n, uint64_t dst_cap)
 {
-    std::vector<std::pair<uint64_t, uint64_t>> win;
+    std::vector<xlzwin::Window> win;
     for (size_t i = 0; i < n; i++) {
-        const xlz_inflate_item &it = items[i];
-        if (!it.in && it.in_len) return false;
-        if (it.dst_off > dst_cap || it.dst_cap > dst_cap - it.dst_off) return false;
-        if (it.dst_cap) win.emplace_back(it.dst_off, it.dst_off + it.dst_cap);
+        if (!items[i].in && items[i].in_len) return false;
+        win.emplace_back(items[i].dst_off, items[i].dst_cap);
     }
-    std::sort(win.begin(), win.end());
-    for (size_t i = 1; i < win.size(); i++)
-        if (win[i - 1].second > win[i].first) return false;
-    return true;
+    return xlzwin::disjoint_within(std::move(win), dst_cap);
 }
 
 // Inflates items[0 .. n) (accepted by inflate_items_ok) into d_dst and waits: by the kernel on `stream` (mode 1, items up
@@ -2956,17 +2916,11 @@ extern "C" int xlz_inflate_batch(xlz_ctx *ctx, const xlz_inflate_item *items, si
     if (ok != XLZ_OK) return ok;
     xlz_inflate_stats acc = {};
     const int st = inflate_run(ctx, items, n, d_dst, results, ctx->stream, xlz_ctx_deflate_mode(ctx) == 2 ? 2 : 1, acc);
-    if (st == XLZ_OK) inflate_stats_set(ctx, acc);
+    if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_inflate, acc);
     return st;
 }
 
-extern "C" int xlz_ctx_set_deflate_mode(xlz_ctx *ctx, int mode)
-{
-    if (!ctx || mode < 0 || mode > 2) return XLZ_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->deflate_mode = mode;
-    return XLZ_OK;
-}
+extern "C" int xlz_ctx_set_deflate_mode(xlz_ctx *ctx, int mode) { return set_mode(ctx, &xlz_ctx::deflate_mode, mode, 2); }
 extern "C" int xlz_ctx_deflate_mode(const xlz_ctx *ctx) { return ctx ? ctx->deflate_mode : XLZ_ERR_BAD_ARG; }
 extern "C" int xlz_ctx_last_inflate_stats(xlz_ctx *ctx, xlz_inflate_stats *out) { return last_stats(ctx, &xlz_ctx::last_inflate, out); }
 
@@ -3890,7 +3844,7 @@ int xlz_internal_decode_device(xlz_ctx *ctx, const xlz_stream_desc *streams, siz
         if (st == XLZ_OK && dest.n_inflate) { // the deflate entries: inflated into the destination, then checked THERE
             xlz_inflate_stats inf = {};
             st = inflate_run(ctx, dest.inflate, dest.n_inflate, dest.d_dst, dest.inflate_res, stream, dest.inflate_mode == 2 ? 2 : 1, inf);
-            if (st == XLZ_OK) inflate_stats_set(ctx, inf);
+            if (st == XLZ_OK) publish(ctx, &xlz_ctx::last_inflate, inf);
         }
         if (st == XLZ_OK && !of_dest.empty()) {
             if (!b) { // (no stream in the call: a batch of none, for the check kernels' scratch alone)

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/xlz.h"
+#include "xlz_windows.h"
 
 // what xlz_decode_batch runs behind its (sub-)batches: the filter steps, then the digests of `ranges` over the filtered
 // bytes.  Exactly one of crc_out (64-bit digests: xlz_decode_batch_checked / _filtered; no XLZ_CHECK_SHA256) and
@@ -132,15 +133,12 @@ template <class F> void parallel_for(size_t n, size_t k, F &&f)
 // length 0 declares no byte.
 inline bool pack_items_ok(const xlz_pack_item *items, size_t n, size_t n_streams, uint64_t dst_cap)
 {
-    std::vector<std::pair<uint64_t, uint64_t>> r;
+    std::vector<xlzwin::Window> r;
     for (size_t i = 0; i < n; i++) {
-        if (items[i].stream >= n_streams || items[i].dst_off > dst_cap || items[i].len > dst_cap - items[i].dst_off) return false;
-        if (items[i].len) r.emplace_back(items[i].dst_off, items[i].dst_off + items[i].len);
+        if (items[i].stream >= n_streams) return false;
+        r.emplace_back(items[i].dst_off, items[i].len); // (one of length 0 too: its dst_off must lie inside dst_cap)
     }
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); i++)
-        if (r[i - 1].second > r[i].first) return false;
-    return true;
+    return xlzwin::disjoint_within(std::move(r), dst_cap);
 }
 
 } // namespace xlzpost

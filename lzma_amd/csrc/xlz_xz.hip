@@ -33,7 +33,6 @@ using xlzcheck::crc32;
 using xlzcheck::crc64;
 
 uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | (uint64_t)le32(p + 4) << 32; }
 
 // variable-length integer (spec 1.2): 7 bits per byte, at most 9 bytes, no trailing zero byte
 bool vli(const uint8_t *p, size_t n, size_t &pos, uint64_t &v)
@@ -249,6 +248,72 @@ int xz_index(const uint8_t *file, size_t len, xlz_xz_block *blocks, size_t max_b
     if (total_uncompressed) *total_uncompressed = uoff;
     return (nb > max_blocks && max_blocks) || (ns > max_steps && max_steps) ? XLZ_ERR_OUT_CAP : XLZ_OK;
 }
+
+// ---------------------------------------------------------------- a block as a stream of the batch ----
+// What xz_decode, xz_read and xz_many share.  The block's descriptor: a raw LZMA2 stream (reader2.go:26-41) that decodes
+// to `out` (NULL: the call has a device destination)
+xlz_stream_desc block_desc(const uint8_t *file, const xlz_xz_block &b, uint8_t *out)
+{
+    xlz_stream_desc d;
+    memset(&d, 0, sizeof d);
+    d.in = file + b.comp_off, d.in_len = (size_t)b.comp_len;
+    d.out = out, d.out_cap = (size_t)b.uncomp_len;
+    d.format = XLZ_FMT_LZMA2_RAW, d.dict_size = b.dict_size;
+    return d;
+}
+
+// The checks the device computes for streams [0, n) under a check mode (xlz_ctx_set_check_mode): 0 none, 1 the CRC32 /
+// CRC64 blocks, 2 the SHA-256 blocks too.  Mode 2 asks for the 32-byte form only where a block needs it (the SHA-256
+// statistics are that form's alone); a CRC then lies little-endian in its first bytes.
+constexpr size_t kNoRange = ~(size_t)0;
+struct BlockChecks {
+    std::vector<xlz_check_range> cr;
+    std::vector<size_t> range_of; // stream -> its range in cr, or kNoRange
+    bool sha = false;             // the digests come as xgot, not as got
+    std::vector<uint64_t> got;
+    std::vector<xlz_digest> xgot;
+    PostWork work(const xlz_filter_step *steps, size_t n_steps) { return {steps, n_steps, cr.data(), cr.size(), sha ? nullptr : got.data(), sha ? xgot.data() : nullptr, true}; }
+    void digest(size_t q, uint8_t dg[32]) const // the bytes of range q as the file's check field holds them
+    {
+        if (sha)
+            memcpy(dg, xgot[q].b, 32);
+        else
+            for (int j = 0; j < 8; j++) dg[j] = (uint8_t)(got[q] >> (8 * j));
+    }
+};
+template <class BlockOf> BlockChecks block_checks(size_t n, int cmode, BlockOf block_of) // block_of(s): the block of stream s
+{
+    BlockChecks c;
+    c.range_of.assign(n, kNoRange);
+    for (size_t s = 0; s < n && cmode == 2; s++) c.sha |= block_of(s).check_type == 10;
+    for (size_t s = 0; s < n && (cmode == 1 || cmode == 2); s++) {
+        const xlz_xz_block &b = block_of(s);
+        if (b.check_type != 1 && b.check_type != 4 && !(c.sha && b.check_type == 10)) continue;
+        xlz_check_range r;
+        memset(&r, 0, sizeof r);
+        r.stream = s, r.off = 0, r.len = b.uncomp_len, r.kind = b.check_type;
+        c.range_of[s] = c.cr.size(), c.cr.push_back(r);
+    }
+    c.got.assign(c.sha ? 0 : c.cr.size(), 0), c.xgot.assign(c.sha ? c.cr.size() : 0, xlz_digest{});
+    return c;
+}
+
+// What the check field of the block of stream s says of its decoded bytes: the device's digest where c has one, else the
+// host's over p (NULL: a device destination, where every check is the device's).  A reserved check type is not verified.
+uint8_t block_check(const uint8_t *file, const xlz_xz_block &b, const BlockChecks &c, size_t s, const uint8_t *p)
+{
+    if (b.check_type != 1 && b.check_type != 4 && b.check_type != 10) return b.check_type ? xlzmany::kCheckUnverified : xlzmany::kCheckGood;
+    uint8_t dg[32] = {};
+    if (c.range_of[s] != kNoRange)
+        c.digest(c.range_of[s], dg);
+    else if (b.check_type == 1)
+        for (uint32_t v = crc32(p, (size_t)b.uncomp_len), j = 0; j < 4; j++) dg[j] = (uint8_t)(v >> (8 * j));
+    else if (b.check_type == 4)
+        for (uint64_t v = crc64(p, (size_t)b.uncomp_len), j = 0; j < 8; j++) dg[j] = (uint8_t)(v >> (8 * j));
+    else
+        xlzcheck::sha256(p, (size_t)b.uncomp_len, dg);
+    return memcmp(dg, file + b.check_off, check_size(b.check_type)) != 0 ? xlzmany::kCheckFailed : xlzmany::kCheckGood;
+}
 } // namespace
 
 // Whole file: index, one batch (block = raw LZMA2 stream, reader2.go:26-41), optional integrity
@@ -305,19 +370,10 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
     if (st != XLZ_OK) return st;
     std::vector<xlz_stream_desc> d(nb);
     std::vector<xlz_result> r(nb);
-    for (size_t i = 0; i < nb; i++) {
-        memset(&d[i], 0, sizeof d[i]);
-        d[i].in = file + blk[i].comp_off;
-        d[i].in_len = (size_t)blk[i].comp_len;
-        d[i].out = out ? out + blk[i].uncomp_off : nullptr;
-        d[i].out_cap = (size_t)blk[i].uncomp_len;
-        d[i].format = XLZ_FMT_LZMA2_RAW;
-        d[i].dict_size = blk[i].dict_size;
-    }
+    for (size_t i = 0; i < nb; i++) d[i] = block_desc(file, blk[i], out ? out + blk[i].uncomp_off : nullptr);
     // check mode 1 (xlz_ctx_set_check_mode; one context): the CRC32 / CRC64 of every block comes from the device with the
-    // batch's results, dg[i] = block i's digest; the other check types stay with the host threads below
-    // check mode 2: the SHA-256 blocks join the range list, xdg[i] = block i's 32 bytes (the device's or the host's, as
-    // xlz_sha256_plan splits them)
+    // batch's results; the other check types stay with the host threads below
+    // check mode 2: the SHA-256 blocks join the range list (the device's or the host's, as xlz_sha256_plan splits them)
     // (a device destination: there are no bytes on the host to check, so as mode 2 whatever the context's mode says)
     const int cmode = !verify ? 0 : d_out ? 2 : n_ctx == 1 ? xlz_ctx_check_mode(ctxs[0]) : 0;
     std::vector<uint64_t> want_out(d_out ? nb : 0), want_in(d_out ? nb : 0), dst_off(d_out ? nb : 0);
@@ -328,39 +384,12 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         return d_out ? xlz_internal_decode_device(ctxs[0], d.data(), nb, r.data(), w, dest) : xlz_internal_decode_batch(ctxs[0], d.data(), nb, r.data(), w);
     };
     const bool dev = cmode == 1 || cmode == 2;
-    bool dev_sha = false;
-    for (size_t i = 0; i < nb && cmode == 2; i++) dev_sha |= blk[i].check_type == 10;
     if (cmode == 2) xlz_internal_sha256_stats_reset(ctxs[0]); // (the statistics of THIS call, also when it has no SHA-256 block)
-    std::vector<uint64_t> dg;
-    std::vector<xlz_digest> xdg;
+    BlockChecks ck = block_checks(nb, cmode, [&](size_t i) -> const xlz_xz_block & { return blk[i]; });
     if (dev) {
-        std::vector<xlz_check_range> cr;
-        std::vector<uint64_t> got;
-        std::vector<size_t> of;
-        for (size_t i = 0; i < nb; i++)
-            if (blk[i].check_type == 1 || blk[i].check_type == 4 || (dev_sha && blk[i].check_type == 10)) {
-                xlz_check_range c;
-                memset(&c, 0, sizeof c);
-                c.stream = i, c.off = 0, c.len = blk[i].uncomp_len, c.kind = blk[i].check_type;
-                cr.push_back(c);
-                of.push_back(i);
-            }
-        got.resize(cr.size());
-        dg.assign(nb, 0);
         xlz_internal_check_stats_reset(ctxs[0]);
         if (chains) xlz_internal_filter_stats_reset(ctxs[0]);
-        // (mode 2 asks for the 32-byte form only where a block needs it: the SHA-256 statistics are that form's alone)
-        std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0);
-        if (dev_sha) xdg.resize(nb);
-        const PostWork w = {fs.data(), nfs, cr.data(), cr.size(), dev_sha ? nullptr : got.data(), dev_sha ? xgot.data() : nullptr, true};
-        st = decode(w);
-        for (size_t k = 0; k < of.size(); k++) {
-            if (dev_sha) {
-                xdg[of[k]] = xgot[k];
-                for (int j = 0; j < 8; j++) got[k] |= (uint64_t)xgot[k].b[j] << (8 * j); // (a CRC: little-endian in b[0..7])
-            }
-            dg[of[k]] = got[k];
-        }
+        st = decode(ck.work(fs.data(), nfs));
     } else if (chains) { // (the digests, if any, on host threads below: over the filtered bytes)
         xlz_internal_filter_stats_reset(ctxs[0]);
         st = decode(PostWork{fs.data(), nfs, nullptr, 0, nullptr, nullptr, true});
@@ -375,32 +404,16 @@ static int xz_decode(xlz_ctx *const *ctxs, size_t n_ctx, const uint8_t *file, si
         if (r[i].out_len != blk[i].uncomp_len || r[i].in_consumed != blk[i].comp_len) return XLZ_ERR_RESULT;
     }
     if (verify) {
-        std::vector<int> bad(nb, 0);
-        xlzpost::parallel_for(nb, xlzpost::host_thread_cap(16), [&](size_t i) {
-            const uint8_t *p = out ? out + blk[i].uncomp_off : nullptr; // (a device destination: every check below is the device's)
-            const uint8_t *c = file + blk[i].check_off;
-            if (dev && (blk[i].check_type == 1 || blk[i].check_type == 4))
-                bad[i] = dg[i] != (blk[i].check_type == 1 ? (uint64_t)le32(c) : le64(c));
-            else if (blk[i].check_type == 1)
-                bad[i] = crc32(p, (size_t)blk[i].uncomp_len) != le32(c);
-            else if (blk[i].check_type == 4)
-                bad[i] = crc64(p, (size_t)blk[i].uncomp_len) != le64(c);
-            else if (blk[i].check_type == 10 && dev_sha)
-                bad[i] = memcmp(xdg[i].b, c, 32) != 0;
-            else if (blk[i].check_type == 10) {
-                uint8_t dg[32];
-                xlzcheck::sha256(p, (size_t)blk[i].uncomp_len, dg);
-                bad[i] = memcmp(dg, c, 32) != 0;
-            } else if (blk[i].check_type != 0)
-                bad[i] = 2; // reserved check types: not verified
-        });
-        if (dev && !dev_sha)
+        std::vector<uint8_t> check(nb);
+        xlzpost::parallel_for(nb, xlzpost::host_thread_cap(16),
+                              [&](size_t i) { check[i] = block_check(file, blk[i], ck, i, out ? out + blk[i].uncomp_off : nullptr); });
+        if (dev && !ck.sha)
             for (size_t i = 0; i < nb; i++)
                 if (blk[i].check_type == 10) xlz_internal_check_stats_host(ctxs[0], 1, blk[i].uncomp_len);
         size_t nu = 0;
         for (size_t i = 0; i < nb; i++) {
-            if (bad[i] == 1) return XLZ_ERR_RESULT;
-            nu += bad[i] == 2;
+            if (check[i] == xlzmany::kCheckFailed) return XLZ_ERR_RESULT;
+            nu += check[i] == xlzmany::kCheckUnverified;
         }
         if (unverified) *unverified = nu;
     }
@@ -482,23 +495,20 @@ static int xz_read(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *range
     xlzcover::Plan p;
     if (!xlzcover::plan(f->ext.data(), f->ext.size(), f->size, ranges, n, out_cap, p)) return XLZ_ERR_BAD_ARG;
     if (!ctx || (p.total && !out && !d_out)) return XLZ_ERR_BAD_ARG;
-    struct Run {
-        uint64_t staged, dst_off, len;
-    };
-    std::vector<Run> runs; // host form: staging bytes [staged, staged + len) -> out + dst_off
+    HostStaging staging(ctx);
+    std::vector<HostStaging::Piece> runs; // host form: the ranges whose destinations touch come down as one piece
     if (!d_out) {
         std::vector<size_t> by_dst;
         for (size_t i = 0; i < n; i++)
             if (p.lens[i]) by_dst.push_back(i);
         std::sort(by_dst.begin(), by_dst.end(), [&](size_t a, size_t b) { return ranges[a].dst_off < ranges[b].dst_off; });
         std::vector<xlz_xz_range> staged(ranges, ranges + n);
-        uint64_t at = 0;
         for (size_t i : by_dst) {
+            staged[i].dst_off = staging.add(p.lens[i]);
             if (!runs.empty() && runs.back().dst_off + runs.back().len == ranges[i].dst_off)
                 runs.back().len += p.lens[i];
             else
-                runs.push_back(Run{at, ranges[i].dst_off, p.lens[i]});
-            staged[i].dst_off = at, at += p.lens[i];
+                runs.push_back({staged[i].dst_off, ranges[i].dst_off, p.lens[i]});
         }
         if (!xlzcover::plan(f->ext.data(), f->ext.size(), f->size, staged.data(), n, p.total, p)) return XLZ_ERR_BAD_ARG;
     }
@@ -526,61 +536,27 @@ static int xz_read(xlz_ctx *ctx, const xlz_xz_file *f, const xlz_xz_range *range
     std::vector<xlz_stream_desc> d(nc);
     std::vector<xlz_result> r(nc);
     std::vector<uint64_t> want_out(nc), want_in(nc);
-    std::vector<xlz_check_range> cr;
-    bool dev_sha = false;
+    const auto block_of = [&](size_t k) -> const xlz_xz_block & { return f->blk[p.blocks[k]]; };
     for (size_t k = 0; k < nc; k++) {
-        const xlz_xz_block &b = f->blk[p.blocks[k]];
-        memset(&d[k], 0, sizeof d[k]);
-        d[k].in = f->file + b.comp_off, d[k].in_len = (size_t)b.comp_len;
-        d[k].out_cap = (size_t)b.uncomp_len, d[k].format = XLZ_FMT_LZMA2_RAW, d[k].dict_size = b.dict_size;
-        want_out[k] = b.uncomp_len, want_in[k] = b.comp_len;
-        if (verify && (b.check_type == 1 || b.check_type == 4 || b.check_type == 10)) {
-            xlz_check_range c;
-            memset(&c, 0, sizeof c);
-            c.stream = k, c.off = 0, c.len = b.uncomp_len, c.kind = b.check_type;
-            cr.push_back(c);
-            dev_sha |= b.check_type == 10;
-        }
+        d[k] = block_desc(f->file, block_of(k), nullptr);
+        want_out[k] = block_of(k).uncomp_len, want_in[k] = block_of(k).comp_len;
     }
-    // (as xlz_xz_decode_device: the 32-byte form only where a block needs it, a CRC little-endian in its first bytes)
-    std::vector<uint64_t> got(dev_sha ? 0 : cr.size());
-    std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0);
-    const PostWork w = {fs.data(), fs.size(), cr.data(), cr.size(), dev_sha ? nullptr : got.data(), dev_sha ? xgot.data() : nullptr, true};
-    void *staging = nullptr;
-    if (!d_out) {
-        const int st = xlz_internal_device_block(ctx, (size_t)p.total, &staging);
-        if (st != XLZ_OK) return st;
-    }
+    BlockChecks ck = block_checks(nc, verify ? 2 : 0, block_of); // (as xlz_xz_decode_device: every check is the device's)
+    const PostWork w = ck.work(fs.data(), fs.size());
+    int st = staging.acquire();
+    if (st != XLZ_OK) return st;
     DeviceDest dest;
-    dest.d_dst = d_out ? d_out : staging, dest.cap = d_out ? out_cap : (size_t)p.total;
+    dest.d_dst = d_out ? d_out : staging.d_dst(), dest.cap = d_out ? out_cap : staging.cap();
     dest.want_out = want_out.data(), dest.want_in = want_in.data();
     dest.items = p.items.data(), dest.n_items = p.items.size(), dest.have_items = true;
-    int st = xlz_internal_decode_device(ctx, d.data(), nc, r.data(), w, dest);
+    st = xlz_internal_decode_device(ctx, d.data(), nc, r.data(), w, dest);
     size_t nu = 0;
-    for (size_t q = 0, k = 0; k < nc && st == XLZ_OK && verify; k++) {
-        const xlz_xz_block &b = f->blk[p.blocks[k]];
-        const uint8_t *c = f->file + b.check_off;
-        if (b.check_type == 0) continue;
-        if (b.check_type != 1 && b.check_type != 4 && b.check_type != 10) {
-            nu++; // reserved check types: not verified
-            continue;
-        }
-        uint8_t dg[32] = {};
-        if (dev_sha)
-            memcpy(dg, xgot[q].b, 32);
-        else
-            for (int j = 0; j < 8; j++) dg[j] = (uint8_t)(got[q] >> (8 * j));
-        q++;
-        if (memcmp(dg, c, check_size(b.check_type)) != 0) st = XLZ_ERR_RESULT;
+    for (size_t k = 0; k < nc && st == XLZ_OK && verify; k++) {
+        const uint8_t check = block_check(f->file, block_of(k), ck, k, nullptr);
+        if (check == xlzmany::kCheckFailed) st = XLZ_ERR_RESULT;
+        nu += check == xlzmany::kCheckUnverified;
     }
-    if (st == XLZ_OK && runs.size() == 1) // (the destinations touch: straight into the caller's buffer)
-        st = xlz_internal_device_block_download(ctx, staging, out + runs[0].dst_off, (size_t)runs[0].len);
-    else if (st == XLZ_OK && !runs.empty()) { // ONE copy of the staging block, scattered on the host
-        std::vector<uint8_t> bounce((size_t)p.total);
-        st = xlz_internal_device_block_download(ctx, staging, bounce.data(), bounce.size());
-        for (size_t j = 0; j < runs.size() && st == XLZ_OK; j++) memcpy(out + runs[j].dst_off, bounce.data() + runs[j].staged, (size_t)runs[j].len);
-    }
-    if (staging) xlz_internal_device_block_release(ctx, staging);
+    if (st == XLZ_OK) st = staging.download(out, runs); // (the destinations touch: ONE run, straight into the caller's buffer)
     if (st != XLZ_OK) return st;
     for (size_t i = 0; i < n && copied; i++) copied[i] = p.lens[i];
     if (unverified) *unverified = nu;
@@ -687,35 +663,14 @@ static int xz_many(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, uint8_
         // (inside the window: the index's total fits dst_cap; a block of no bytes has no place -- its window may be one of no
         //  bytes, which may point anywhere)
         const uint64_t at = blk[s].uncomp_len ? files[m.file_of[s]].dst_off + blk[s].uncomp_off : 0;
-        memset(&d[s], 0, sizeof d[s]);
         memset(&r[s], 0, sizeof r[s]);
-        d[s].in = files[m.file_of[s]].file + blk[s].comp_off;
-        d[s].in_len = (size_t)blk[s].comp_len;
-        d[s].out = device ? nullptr : out + at;
-        d[s].out_cap = (size_t)blk[s].uncomp_len;
-        d[s].format = XLZ_FMT_LZMA2_RAW;
-        d[s].dict_size = blk[s].dict_size;
+        d[s] = block_desc(files[m.file_of[s]].file, blk[s], device ? nullptr : out + at);
         if (device) want_out[s] = blk[s].uncomp_len, want_in[s] = blk[s].comp_len, dst_off[s] = at;
     }
     const int cmode = !verify ? 0 : device ? 2 : xlz_ctx_check_mode(ctx);
     const bool dev = cmode == 1 || cmode == 2;
-    bool dev_sha = false;
-    for (size_t s = 0; s < S && cmode == 2; s++) dev_sha |= blk[s].check_type == 10;
-    std::vector<xlz_check_range> cr;
-    std::vector<size_t> range_of(S, ~(size_t)0); // stream -> its range in cr
-    for (size_t s = 0; s < S && dev; s++)
-        if (blk[s].check_type == 1 || blk[s].check_type == 4 || (dev_sha && blk[s].check_type == 10)) {
-            xlz_check_range c;
-            memset(&c, 0, sizeof c);
-            c.stream = s, c.off = 0, c.len = blk[s].uncomp_len, c.kind = blk[s].check_type;
-            range_of[s] = cr.size();
-            cr.push_back(c);
-        }
-    // (the 32-byte form only where a block needs it, a CRC little-endian in its first bytes: as xz_decode)
-    std::vector<uint64_t> got(dev_sha ? 0 : cr.size(), 0);
-    std::vector<xlz_digest> xgot(dev_sha ? cr.size() : 0, xlz_digest{});
-    const PostWork w = {fs.data(), fs.size(), cr.data(), cr.size(), !cr.empty() && !dev_sha ? got.data() : nullptr,
-                        !cr.empty() && dev_sha ? xgot.data() : nullptr, true};
+    BlockChecks ck = block_checks(S, cmode, [&](size_t s) -> const xlz_xz_block & { return blk[s]; });
+    const PostWork w = ck.work(fs.data(), fs.size());
     int st = XLZ_OK;
     if (S && device) {
         DeviceDest dest;
@@ -736,27 +691,9 @@ static int xz_many(xlz_ctx *ctx, const xlz_xz_many_file *files, size_t n, uint8_
     for (size_t s = 0; s < S; s++) block_st[s] = xlzmany::block_status(r[s].status, r[s].out_len, r[s].in_consumed, blk[s].uncomp_len, blk[s].comp_len);
     if (verify)
         xlzpost::parallel_for(S, xlzpost::host_thread_cap(16), [&](size_t s) {
-            if (block_st[s] < 0) return;
-            const xlz_xz_block &b = blk[s];
-            const uint8_t *p = device ? nullptr : d[s].out; // (the device form: every check below is the device's)
-            const uint8_t *c = files[m.file_of[s]].file + b.check_off;
-            uint8_t dg[32] = {};
-            if (range_of[s] != ~(size_t)0 && dev_sha)
-                memcpy(dg, xgot[range_of[s]].b, 32);
-            else if (range_of[s] != ~(size_t)0)
-                for (int j = 0; j < 8; j++) dg[j] = (uint8_t)(got[range_of[s]] >> (8 * j));
-            else if (b.check_type == 1)
-                for (uint32_t v = crc32(p, (size_t)b.uncomp_len), j = 0; j < 4; j++) dg[j] = (uint8_t)(v >> (8 * j));
-            else if (b.check_type == 4)
-                for (uint64_t v = crc64(p, (size_t)b.uncomp_len), j = 0; j < 8; j++) dg[j] = (uint8_t)(v >> (8 * j));
-            else if (b.check_type == 10)
-                xlzcheck::sha256(p, (size_t)b.uncomp_len, dg);
-            if (b.check_type == 1 || b.check_type == 4 || b.check_type == 10)
-                check[s] = memcmp(dg, c, check_size(b.check_type)) != 0 ? xlzmany::kCheckFailed : xlzmany::kCheckGood;
-            else if (b.check_type != 0)
-                check[s] = xlzmany::kCheckUnverified; // reserved check types: not verified
+            if (block_st[s] >= 0) check[s] = block_check(files[m.file_of[s]].file, blk[s], ck, s, d[s].out); // (the device form: no out, every check is the device's)
         });
-    for (size_t s = 0; s < S && verify && dev && !dev_sha; s++) // (check mode 1: the SHA-256 blocks stayed with the host threads above)
+    for (size_t s = 0; s < S && verify && dev && !ck.sha; s++) // (check mode 1: the SHA-256 blocks stayed with the host threads above)
         if (blk[s].check_type == 10 && block_st[s] >= 0) xlz_internal_check_stats_host(ctx, 1, blk[s].uncomp_len);
     for (size_t i = 0; i < n; i++) {
         if (in_batch[i]) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/xlz.h"
+#include "xlz_windows.h"
 
 namespace xlzmany {
 
@@ -18,16 +19,10 @@ namespace xlzmany {
 // share a byte.  A window with dst_cap == 0 declares no byte, wherever its dst_off points.
 inline bool windows_ok(const xlz_xz_many_file *f, size_t n, uint64_t out_cap)
 {
-    std::vector<std::pair<uint64_t, uint64_t>> w;
-    for (size_t i = 0; i < n; i++) {
-        if (!f[i].dst_cap) continue;
-        if (f[i].dst_off > out_cap || f[i].dst_cap > out_cap - f[i].dst_off) return false;
-        w.emplace_back(f[i].dst_off, f[i].dst_off + f[i].dst_cap);
-    }
-    std::sort(w.begin(), w.end());
-    for (size_t i = 1; i < w.size(); i++)
-        if (w[i - 1].second > w[i].first) return false;
-    return true;
+    std::vector<xlzwin::Window> w;
+    for (size_t i = 0; i < n; i++)
+        if (f[i].dst_cap) w.emplace_back(f[i].dst_off, f[i].dst_cap);
+    return xlzwin::disjoint_within(std::move(w), out_cap);
 }
 
 // Windows of sizes[0 .. n) back to back, in order: off[i] = the first multiple of align (>= 1) at or behind the end of
@@ -35,20 +30,7 @@ inline bool windows_ok(const xlz_xz_many_file *f, size_t n, uint64_t out_cap)
 // unless it fits).
 inline bool layout(const uint64_t *sizes, size_t n, uint64_t align, uint64_t *off, uint64_t *total)
 {
-    const uint64_t top = ~(uint64_t)0;
-    uint64_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t over = at % align;
-        if (over) {
-            if (align - over > top - at) return false;
-            at += align - over;
-        }
-        off[i] = at;
-        if (sizes[i] > top - at) return false;
-        at += sizes[i];
-    }
-    *total = at;
-    return true;
+    return xlzwin::back_to_back(sizes, n, align, off, total);
 }
 
 // Which stream of the one batch a (file, block) is: the files that got as far as the batch, in order, each with its

@@ -95,12 +95,12 @@ static int zip_extract(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_wan
     }
     // ---- the plan: what settles an entry before the batch, the streams, the stored spans, the pack items
     std::vector<uint64_t> dst(n, 0);
-    uint64_t staged = 0; // host form: the staging block's size
+    HostStaging staging(ctx); // host form: the wanted sizes back to back
     for (size_t i = 0; i < n; i++) {
         const xlz_zip_entry &x = e[wants[i].entry];
         if (!has_bytes(x)) continue;
         dst[i] = wants[i].dst_off;
-        if (!device && wants[i].dst_cap >= x.size) dst[i] = staged, staged += x.size; // (no wrap: disjoint windows of out_cap hold them)
+        if (!device && wants[i].dst_cap >= x.size) dst[i] = staging.add(x.size);
     }
     Plan p;
     const int deflate_mode = xlz_ctx_deflate_mode ? xlz_ctx_deflate_mode(ctx) : 0;
@@ -124,13 +124,11 @@ static int zip_extract(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_wan
     std::vector<uint64_t> got(cr.size(), 0);
     std::vector<DeviceCopy> copies;
     for (const Span &s : p.spans) copies.push_back(DeviceCopy{s.dst, a->file + s.src_off, s.len});
-    int st = XLZ_OK;
-    void *staging = nullptr;
-    if (!device && staged) st = xlz_internal_device_block(ctx, (size_t)staged, &staging);
+    int st = staging.acquire();
     if (st == XLZ_OK && (ns || !copies.empty() || !p.inflate.empty())) {
         const PostWork w = {nullptr, 0, cr.data(), cr.size(), got.data(), nullptr, true};
         DeviceDest dest;
-        dest.d_dst = device ? d_out : staging, dest.cap = device ? out_cap : (size_t)staged;
+        dest.d_dst = device ? d_out : staging.d_dst(), dest.cap = device ? out_cap : staging.cap();
         dest.want_out = want_out.data();
         dest.items = p.items.data(), dest.n_items = p.items.size(), dest.have_items = true, dest.tolerant = true;
         dest.copies = copies.data(), dest.n_copies = copies.size(), dest.gather_copies = true, dest.copy_uploads = &xs.stored_uploads;
@@ -149,17 +147,7 @@ static int zip_extract(xlz_ctx *ctx, const xlz_zip_archive *a, const xlz_zip_wan
         if (range_of[i] != kNone && sst[i] == XLZ_OK) dig[i] = (uint32_t)got[range_of[i]] == x.crc ? kDigestGood : kDigestBad;
         v[i] = verdict(p.pre[i], x, sst[i], dig[i], verify != 0);
     }
-    if (st == XLZ_OK && staging) { // ONE copy of the staging block, the good entries scattered on the host
-        std::vector<uint8_t> bounce((size_t)staged);
-        st = xlz_internal_device_block_download(ctx, staging, bounce.data(), bounce.size());
-        for (size_t i = 0; i < n && st == XLZ_OK; i++)
-            if (v[i].status == XLZ_OK && v[i].out_len) memcpy(out + wants[i].dst_off, bounce.data() + dst[i], (size_t)v[i].out_len);
-    }
-    if (staging) xlz_internal_device_block_release(ctx, staging);
-    for (size_t i = 0; i < n; i++) {
-        results[i] = st == XLZ_OK ? v[i] : xlz_zip_file_result{st, 0, 0};
-        xs.failed_entries += results[i].status != XLZ_OK, xs.copied_bytes += results[i].out_len;
-    }
+    st = xlz_internal_extract_finish(staging, st, wants, dst.data(), v, out, results, xs); // (ONE copy of the staging block, the good entries scattered)
     xlz_internal_zip_extract_stats_set(ctx, xs);
     return st;
 }
