@@ -1272,6 +1272,94 @@ typedef struct xlz_zip_extract_stats {
 } xlz_zip_extract_stats;
 int xlz_ctx_last_zip_extract_stats(xlz_ctx *ctx, xlz_zip_extract_stats *out);
 
+/* ---- Adler-32 of ranges of a device buffer (lzma_amd/csrc/xlz_adler_dev.hip) ----
+ * RFC 1950 section 8.2: A = 1 + the sum of the bytes, B = the sum of the running A, both mod 65521; the digest is
+ * B << 16 | A.  The scheme (rows of 64 lanes x 16 bytes, one wave per segment of 128 KiB, a fold by the combine rule) and
+ * how long the modulo is deferred are at the head of lzma_amd/csrc/xlz_adler_dev.h.                                    */
+typedef struct xlz_adler_range { uint64_t off, len; } xlz_adler_range;
+/* Adler-32 of n ranges of a device buffer of the context's device, digests[i] for ranges[i]; the ranges may overlap and
+ * come in any order, they start and end at any byte, d_buf needs no alignment; a range of length 0 has the digest 1.  No
+ * byte outside a range is read.  The call waits for its kernels.  XLZ_ERR_BAD_ARG: a NULL argument with n > 0; a range
+ * outside [0, buf_len); d_buf is not device memory of the context's device, or buf_len reaches past its allocation.
+ * XLZ_ERR_UNSUPPORTED: more than 2^32 - 1 ranges or segments (512 TiB) in one call.  n = 0 is XLZ_OK.                     */
+int xlz_adler32_device(xlz_ctx *ctx, const void *d_buf, size_t buf_len, const xlz_adler_range *ranges, size_t n, uint32_t *digests);
+/* Host only.  The digest of `adler`'s bytes followed by p[0 .. n) (adler = 1: of p alone) ...                           */
+uint32_t xlz_adler32_host(uint32_t adler, const uint8_t *p, size_t n);
+/* ... and adler32(A || B) from a = adler32(A), b = adler32(B) and len_b = |B|, like xlz_crc32_combine.                  */
+uint32_t xlz_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b);
+
+/* ---- gzip files, BGZF files and zlib streams as one batch (lzma_amd/csrc/xlz_gz.h, xlz_gz.hip) ----
+ * A gzip file (RFC 1952) is one or more members; a BGZF file (bgzip, BAM, tabix) is a gzip file whose every member
+ * announces its own size, so that all of its blocks are known without inflating a byte; a zlib stream (RFC 1950) is one
+ * deflate stream with a two-byte header and an Adler-32 behind it.  The formats, what is which status and the verdict
+ * are described at the head of lzma_amd/csrc/xlz_gz.h:
+ *   XLZ_ERR_RESULT          wrong magic, a bad zlib header, bytes that are neither zero nor a member behind a member, invalid
+ *                           deflate data, a size or check value that differs, ANY failure of a BGZF block
+ *   XLZ_ERR_UNSUPPORTED     a compression method other than 8, a reserved FLG bit, a zlib stream that wants a dictionary
+ *   XLZ_ERR_UNEXPECTED_EOF  the input ends inside a header, a deflate stream or a trailer
+ *   XLZ_ERR_OUT_CAP         the file decodes to more than its dst_cap
+ * WHAT THIS MAKES FAST, and what not: every stream is inflated by ONE wave (xlz_inflate_batch's machinery), and a lone wave
+ * is slower than a host core.  BGZF files and batches of many files or streams fill the device; one ordinary
+ * single-member .gz of a large file is the host's job -- a member above the launch-length cap goes to host threads anyway
+ * -- and stays so.                                                                                                   */
+enum { XLZ_GZ_AUTO = 0, XLZ_GZ_GZIP = 1, XLZ_GZ_ZLIB = 2 }; /* AUTO: 1f 8b -> gzip, else a valid zlib header -> zlib, else
+                                                               XLZ_ERR_RESULT (fewer than 2 bytes: XLZ_ERR_UNEXPECTED_EOF) */
+enum { XLZ_GZ_F_BGZF = 1, XLZ_GZ_F_NAME = 2, XLZ_GZ_F_COMMENT = 4, XLZ_GZ_F_HCRC = 8 };
+typedef struct xlz_gz_info {
+    uint32_t format, flags; /* resolved format; flags of the first member                                         */
+    uint64_t members;       /* BGZF: blocks, empty ones included; otherwise 0 = not known before decoding          */
+    uint64_t size_hint;     /* BGZF: the sum of the blocks' ISIZE (exact for a sound file); gzip: the last four bytes
+                               (what gzip -l prints: exact for ONE member below 4 GiB); zlib: 0                    */
+    uint32_t mtime;         /* of the first member                                                                */
+    uint32_t name_off, name_len; /* its FNAME inside the input, without the zero byte (XLZ_GZ_F_NAME)             */
+    uint32_t reserved;
+} xlz_gz_info;
+/* Host only: what the headers say (no FHCRC is compared, nothing is inflated).  -> XLZ_OK or the header's status;
+ * XLZ_ERR_BAD_ARG: out is NULL, in is NULL with in_len > 0, an unknown format.                                        */
+int xlz_gz_probe(const uint8_t *in, size_t in_len, uint32_t format, xlz_gz_info *out);
+typedef struct xlz_gz_file {
+    const uint8_t *in;  /* host memory: the file or stream                                                        */
+    uint64_t in_len;
+    uint64_t dst_off;   /* its window in the destination                                                          */
+    uint64_t dst_cap;
+    uint32_t format;    /* XLZ_GZ_AUTO / _GZIP / _ZLIB                                                            */
+    uint32_t reserved;
+} xlz_gz_file;
+typedef struct xlz_gz_result {
+    int32_t status;
+    uint32_t members;     /* members or BGZF blocks that were inflated                                            */
+    uint64_t out_len;     /* bytes at dst_off; 0 unless status == XLZ_OK (the window then holds unspecified bytes) */
+    uint64_t in_consumed; /* gzip: in_len; zlib: where the trailer ended; 0 unless status == XLZ_OK               */
+} xlz_gz_result;
+/* Host only, the serial twin: one file into host memory.  The call returns XLZ_OK whenever it ran, the file's outcome is
+ * *r.  XLZ_ERR_BAD_ARG: r is NULL, a NULL pointer with a length behind it, an unknown format.                          */
+int xlz_gz_decode_host(const uint8_t *in, size_t in_len, uint32_t format, uint8_t *out, size_t out_cap, int verify, xlz_gz_result *r);
+/* Many files as ONE batch into one caller-owned device buffer.  ROUND 1 inflates every block of every BGZF file, the first
+ * member of every ordinary gzip file and every zlib stream as the items of one xlz_inflate_batch run (one gathered upload
+ * below 256 MiB, one launch sequence; items above the launch-length cap, and all of them in deflate mode 2, on host
+ * threads); round k inflates member k of the ordinary gzip files that still have one -- it begins where member k - 1
+ * ended, so a file of m ordinary members costs m rounds.  With verify on, the CRC32 of every gzip member goes through the
+ * check kernels and the Adler-32 of every zlib stream through xlz_adler32_device's kernels, over the destination: only
+ * digests leave the device.  results[i] is what file i gets when it is passed alone; one bad file never fails the call,
+ * which returns XLZ_OK whenever it ran.  Like xlz_inflate_batch the call does not look at whether the deflate mode is 0.
+ * XLZ_ERR_BAD_ARG, with nothing written: NULL arguments with n > 0; a file without a pointer to its length; a window that
+ * does not fit dst_cap, two windows that share a byte; an unknown format; d_dst is not device memory of the context's
+ * device.  n = 0 is XLZ_OK.  Nothing outside the files' windows is written.                                          */
+int xlz_gz_decode_many_device(xlz_ctx *ctx, const xlz_gz_file *files, size_t n, void *d_dst, size_t dst_cap, int verify, xlz_gz_result *results);
+/* The same into host memory: the windows lie back to back in one staging block of the context's pool, which comes down
+ * in ONE copy; only the good files are scattered into dst.                                                           */
+int xlz_gz_decode_many(xlz_ctx *ctx, const xlz_gz_file *files, size_t n, uint8_t *dst, size_t dst_cap, int verify, xlz_gz_result *results);
+/* Of the most recent xlz_gz_decode_many / xlz_gz_decode_many_device on `ctx` that ran.                                */
+typedef struct xlz_gz_stats {
+    uint64_t files, failed_files, bgzf_files;
+    uint64_t members;                  /* members and BGZF blocks inflated                                        */
+    uint64_t device_items, host_items; /* by the kernel; on host threads                                          */
+    uint64_t crc_ranges, adler_ranges; /* members / streams whose digest was formed (verify on; an empty one's on the host) */
+    uint32_t rounds, uploads;          /* inflate runs; transfers of gathered inputs                              */
+    double adler_kernel_ms;
+} xlz_gz_stats;
+int xlz_ctx_last_gz_stats(xlz_ctx *ctx, xlz_gz_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

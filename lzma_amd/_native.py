@@ -68,6 +68,8 @@ EXPORTS = [
     "xlz_zip_open", "xlz_zip_close", "xlz_zip_archive_info", "xlz_zip_archive_entries", "xlz_zip_extract_layout", "xlz_zip_extract",
     "xlz_zip_extract_device", "xlz_ctx_last_zip_extract_stats",
     "xlz_inflate_host", "xlz_inflate_batch", "xlz_ctx_set_deflate_mode", "xlz_ctx_deflate_mode", "xlz_ctx_last_inflate_stats",
+    "xlz_adler32_device", "xlz_adler32_host", "xlz_adler32_combine",
+    "xlz_gz_probe", "xlz_gz_decode_host", "xlz_gz_decode_many_device", "xlz_gz_decode_many", "xlz_ctx_last_gz_stats",
 ]
 
 
@@ -256,6 +258,35 @@ class InflateStats(ctypes.Structure):
     _fields_ = [("device_items", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("host_items", ctypes.c_uint64),
                 ("host_bytes", ctypes.c_uint64), ("failed_items", ctypes.c_uint64), ("uploads", ctypes.c_uint32),
                 ("launches", ctypes.c_uint32)]
+
+
+class AdlerRange(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
+GZ_AUTO, GZ_GZIP, GZ_ZLIB = 0, 1, 2
+GZ_F_BGZF, GZ_F_NAME, GZ_F_COMMENT, GZ_F_HCRC = 1, 2, 4, 8
+
+
+class GzInfo(ctypes.Structure):
+    _fields_ = [("format", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("members", ctypes.c_uint64), ("size_hint", ctypes.c_uint64),
+                ("mtime", ctypes.c_uint32), ("name_off", ctypes.c_uint32), ("name_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class GzFile(ctypes.Structure):
+    _fields_ = [("inp", ctypes.c_void_p), ("in_len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64),
+                ("format", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class GzResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("members", ctypes.c_uint32), ("out_len", ctypes.c_uint64), ("in_consumed", ctypes.c_uint64)]
+
+
+class GzStats(ctypes.Structure):
+    _fields_ = [("files", ctypes.c_uint64), ("failed_files", ctypes.c_uint64), ("bgzf_files", ctypes.c_uint64), ("members", ctypes.c_uint64),
+                ("device_items", ctypes.c_uint64), ("host_items", ctypes.c_uint64), ("crc_ranges", ctypes.c_uint64),
+                ("adler_ranges", ctypes.c_uint64), ("rounds", ctypes.c_uint32), ("uploads", ctypes.c_uint32),
+                ("adler_kernel_ms", ctypes.c_double)]
 
 
 class ZipEntry(ctypes.Structure):
@@ -537,6 +568,17 @@ def lib():
         L.xlz_zip_extract.argtypes = [vp, vp, ctypes.POINTER(ZipWant), sz, vp, sz, i32, ctypes.POINTER(ZipFileResult)]
         L.xlz_zip_extract_device.argtypes = L.xlz_zip_extract.argtypes
         L.xlz_ctx_last_zip_extract_stats.argtypes = [vp, ctypes.POINTER(ZipExtractStats)]
+    if hasattr(L, "xlz_gz_probe"):  # (an older library loaded through XLZ_SO reads no gzip)
+        L.xlz_adler32_device.argtypes = [vp, vp, sz, ctypes.POINTER(AdlerRange), sz, ctypes.POINTER(ctypes.c_uint32)]
+        L.xlz_adler32_host.restype = ctypes.c_uint32
+        L.xlz_adler32_host.argtypes = [ctypes.c_uint32, vp, sz]
+        L.xlz_adler32_combine.restype = ctypes.c_uint32
+        L.xlz_adler32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+        L.xlz_gz_probe.argtypes = [vp, sz, ctypes.c_uint32, ctypes.POINTER(GzInfo)]
+        L.xlz_gz_decode_host.argtypes = [vp, sz, ctypes.c_uint32, vp, sz, i32, ctypes.POINTER(GzResult)]
+        L.xlz_gz_decode_many_device.argtypes = [vp, ctypes.POINTER(GzFile), sz, vp, sz, i32, ctypes.POINTER(GzResult)]
+        L.xlz_gz_decode_many.argtypes = L.xlz_gz_decode_many_device.argtypes
+        L.xlz_ctx_last_gz_stats.argtypes = [vp, ctypes.POINTER(GzStats)]
     _lib = L
     return L
 

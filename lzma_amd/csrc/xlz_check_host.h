@@ -23,6 +23,11 @@ void xlz_internal_xz_many_stats_set(xlz_ctx *ctx, const xlz_xz_many_stats &s);
 void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats &s);
 // what xlz_ctx_last_zip_extract_stats reports: set by every xlz_zip_extract / xlz_zip_extract_device that ran
 void xlz_internal_zip_extract_stats_set(xlz_ctx *ctx, const xlz_zip_extract_stats &s);
+// what xlz_ctx_last_gz_stats reports: set by every xlz_gz_decode_many / xlz_gz_decode_many_device that ran
+void xlz_internal_gz_stats_set(xlz_ctx *ctx, const xlz_gz_stats &s);
+// xlz_adler32_device behind its argument tests of the context and the pointer (the ranges lie inside buf_len); *ms
+// (optional) += the kernels' time
+int xlz_internal_adler_run(xlz_ctx *ctx, const void *d_buf, size_t buf_len, const xlz_adler_range *ranges, size_t n, uint32_t *digests, double *ms);
 // the device steps of xlz_tar_scan_device (xlz_tar_dev.hip) on the context's stream: the flags of the image's complete
 // 512-byte blocks -> flags_out, and blocks idx[0 .. n) dense -> out_host; *ms = the kernel's time.  What
 // xlz_ctx_last_tar_stats reports is set by every scan that ran.

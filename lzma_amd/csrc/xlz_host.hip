@@ -35,6 +35,7 @@
 #include "xlz_pack_dev.h"
 #include "xlz_bcj2_dev.h"
 #include "xlz_inflate_dev.h"
+#include "xlz_adler_dev.h"
 #include "xlz_7z_files.h"
 #include "xlz_xz_many.h"
 
@@ -260,6 +261,7 @@ struct xlz_ctx {
     xlz_7z_extract_stats last_7z_extract = {}; // xlz_ctx_last_7z_extract_stats (xlz_7z_extract.hip)
     xlz_zip_extract_stats last_zip_extract = {}; // xlz_ctx_last_zip_extract_stats (xlz_zip.hip)
     xlz_tar_stats last_tar = {}; // xlz_ctx_last_tar_stats (xlz_tar_dev.hip)
+    xlz_gz_stats last_gz = {}; // xlz_ctx_last_gz_stats (xlz_gz.hip)
     // BCJ2 folders (xlz_bcj2_dev.hip): xlz_ctx_set_bcj2_mode, xlz_ctx_last_bcj2_stats
     int bcj2_mode = 0;
     xlz_bcj2_stats last_bcj2 = {};
@@ -2580,6 +2582,75 @@ int xlz_internal_tar_gather_device(xlz_ctx *ctx, const void *d_image, uint64_t l
 }
 extern "C" int xlz_ctx_last_tar_stats(xlz_ctx *ctx, xlz_tar_stats *out) { return last_stats(ctx, &xlz_ctx::last_tar, out); }
 void xlz_internal_tar_stats_set(xlz_ctx *ctx, const xlz_tar_stats &s) { publish(ctx, &xlz_ctx::last_tar, s); }
+
+// ---------------------------------------------------------------- Adler-32 of device ranges ----
+namespace xlz {
+int adler_launch(const uint8_t *buf, const xlzchk::DevRange *ranges, uint32_t n_ranges, uint32_t total_segs, uint32_t *seg_vals, uint32_t *digests,
+                 int num_cus, hipStream_t stream);
+}
+// xlz_check_host.h.  The kernels read aligned lines: their base is d_buf rounded down to 16, every range shifted by the
+// bytes in front of it (as xlzpost::dest_resolve has it for the CRC kernels).  Empty ranges are settled here.
+int xlz_internal_adler_run(xlz_ctx *ctx, const void *d_buf, size_t buf_len, const xlz_adler_range *ranges, size_t n, uint32_t *digests, double *ms)
+{
+    using xlzchk::DevRange;
+    const uint64_t mis = (uintptr_t)d_buf & 15;
+    std::vector<DevRange> tab;
+    uint64_t segs = 0;
+    for (size_t i = 0; i < n; i++) {
+        digests[i] = 1;
+        if (!ranges[i].len) continue;
+        const uint64_t off = ranges[i].off + mis, ns = xlzchk::range_segments(off, ranges[i].len);
+        if (segs + ns > 0xFFFFFFFFull || tab.size() >= 0xFFFFFFFFull) return XLZ_ERR_UNSUPPORTED;
+        tab.push_back(DevRange{off, ranges[i].len, (uint32_t)segs, (uint32_t)ns, (uint32_t)tab.size(), 0});
+        segs += ns;
+    }
+    if (tab.empty()) return XLZ_OK;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    TarScratch s(ctx);
+    const size_t tab_bytes = tab.size() * sizeof(DevRange), seg_bytes = (size_t)segs * 4, dig_bytes = tab.size() * 4;
+    uint8_t *dev = static_cast<uint8_t *>(s.blk[0] = ctx->pool.take(tab_bytes + seg_bytes + dig_bytes, false));
+    if (!dev) return XLZ_ERR_DEVICE;
+    HIP_TRY(hipMemcpyAsync(dev, tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<uint32_t> dense(tab.size());
+    uint32_t *d_seg = reinterpret_cast<uint32_t *>(dev + tab_bytes), *d_dig = reinterpret_cast<uint32_t *>(dev + tab_bytes + seg_bytes);
+    double t = 0;
+    const int st = s.run(
+        "adler kernels",
+        [&] {
+            return xlz::adler_launch(static_cast<const uint8_t *>(d_buf) - mis, reinterpret_cast<const DevRange *>(dev), (uint32_t)tab.size(),
+                                     (uint32_t)segs, d_seg, d_dig, ctx->num_cus, ctx->stream) == 0;
+        },
+        dense.data(), d_dig, dig_bytes, &t);
+    if (st != XLZ_OK) return st;
+    for (size_t i = 0, k = 0; i < n; i++)
+        if (ranges[i].len) digests[i] = dense[k++];
+    if (ms) *ms += t;
+    return XLZ_OK;
+}
+// xlz_adler32_device with the kernels' time by HIP events -> *ms.  Not part of the C ABI, but exported: tools/gz_bench.py
+// runs the kernels alone through it.
+extern "C" int xlz_internal_adler32_device_timed(xlz_ctx *ctx, const void *d_buf, size_t buf_len, const xlz_adler_range *ranges, size_t n,
+                                                 uint32_t *digests, double *ms)
+{
+    if (!ms) return XLZ_ERR_BAD_ARG;
+    *ms = 0;
+    if (!ctx || !n || !ranges || !digests || !d_buf) return XLZ_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (ranges[i].off > buf_len || ranges[i].len > buf_len - ranges[i].off) return XLZ_ERR_BAD_ARG;
+    const int ok = device_dst_ok(ctx, d_buf, buf_len);
+    return ok != XLZ_OK ? ok : xlz_internal_adler_run(ctx, d_buf, buf_len, ranges, n, digests, ms);
+}
+extern "C" int xlz_adler32_device(xlz_ctx *ctx, const void *d_buf, size_t buf_len, const xlz_adler_range *ranges, size_t n, uint32_t *digests)
+{
+    double ms;
+    return ctx && !n ? (int)XLZ_OK : xlz_internal_adler32_device_timed(ctx, d_buf, buf_len, ranges, n, digests, &ms);
+}
+extern "C" uint32_t xlz_adler32_host(uint32_t adler, const uint8_t *p, size_t n) { return p || !n ? xlzadl::host_update(adler, p, n) : adler; }
+extern "C" uint32_t xlz_adler32_combine(uint32_t a, uint32_t b, uint64_t len_b) { return xlzadl::combine(a, b, len_b); }
+// gzip / BGZF / zlib files as one batch (xlz_gz.hip: xlz_gz_decode_many / xlz_gz_decode_many_device)
+extern "C" int xlz_ctx_last_gz_stats(xlz_ctx *ctx, xlz_gz_stats *out) { return last_stats(ctx, &xlz_ctx::last_gz, out); }
+void xlz_internal_gz_stats_set(xlz_ctx *ctx, const xlz_gz_stats &s) { publish(ctx, &xlz_ctx::last_gz, s); }
 
 // ---------------------------------------------------------------- BCJ2 folders ----
 namespace xlz {
