@@ -1360,6 +1360,82 @@ typedef struct xlz_gz_stats {
 } xlz_gz_stats;
 int xlz_ctx_last_gz_stats(xlz_ctx *ctx, xlz_gz_stats *out);
 
+/* ---- .bz2 files as one batch (lzma_amd/csrc/xlz_bz2_dev.h, xlz_bz2.h, xlz_bz2.hip) ----
+ * A .bz2 file is one or more streams, each a chain of independent blocks of at most level x 100 000 bytes; every block
+ * opens with a 48-bit magic that is found at any bit offset without decoding anything, so ONE large file is a batch of
+ * blocks, as many files are.  The format, the lane scheme and which defect is which status are at the head of
+ * xlz_bz2_dev.h; the scan, the chain rule and the verdict at the head of xlz_bz2.h.  A file's outcome is that of a serial
+ * reader which joins concatenated streams:
+ *   XLZ_ERR_RESULT          a defect in the first stream: a bad header, a damaged block, a CRC that differs
+ *   XLZ_ERR_UNSUPPORTED     a randomised block in the first stream
+ *   XLZ_ERR_UNEXPECTED_EOF  the input ends inside a stream with no defect in front of the end
+ *   XLZ_ERR_OUT_CAP         the file decodes to more than its dst_cap: out_len is then THE TRUE DECODED SIZE (a .bz2 file
+ *                           does not state it), nothing of the file was written in a call of one round, and the caller
+ *                           retries once with exact room
+ *   XLZ_OK                  also when, behind at least one complete stream, a stream with a defect was IGNORED together
+ *                           with everything behind it: in_consumed is the end of the last good stream and shows it
+ * WHAT THIS MAKES FAST, and what not: every block is decoded by ONE wave, and a lone wave is much slower than a host core.
+ * Files of many blocks and batches of many files fill the device; a file of a few blocks is the host's job.            */
+typedef struct xlz_bz2_info {
+    uint32_t level, reserved; /* of the first stream: '1'..'9'                                                        */
+    uint64_t candidates;      /* block magics found, at any bit offset: an upper bound of the blocks                   */
+    uint64_t streams;         /* end magics found                                                                     */
+    uint64_t size_hint;       /* candidates x level x 100 000: what the file decodes to at most when no run was folded  */
+    uint64_t size_bound;      /* what it can decode to at all: every block all runs of 255 + 4                          */
+} xlz_bz2_info;
+/* Host only: the first header and the scan, nothing decoded.  -> XLZ_OK, XLZ_ERR_UNEXPECTED_EOF (fewer than 4 bytes),
+ * XLZ_ERR_RESULT (no "BZh1".."BZh9"); XLZ_ERR_BAD_ARG: out is NULL, in is NULL with in_len > 0.                        */
+int xlz_bz2_probe(const uint8_t *in, size_t in_len, xlz_bz2_info *out);
+typedef struct xlz_bz2_file {
+    const uint8_t *in; /* host memory: the file                                                                       */
+    uint64_t in_len;
+    uint64_t dst_off;  /* its window in the destination                                                               */
+    uint64_t dst_cap;
+} xlz_bz2_file;
+typedef struct xlz_bz2_result {
+    int32_t status;
+    uint32_t blocks;      /* blocks of the kept streams                                                               */
+    uint64_t out_len;     /* bytes at dst_off (XLZ_OK); the true decoded size (XLZ_ERR_OUT_CAP); else 0                */
+    uint64_t in_consumed; /* where the last kept stream ended; 0 unless status == XLZ_OK                              */
+    uint32_t streams;     /* kept streams                                                                             */
+    uint32_t reserved;
+} xlz_bz2_result;
+/* Host only, the serial twin: one file into host memory.  The call returns XLZ_OK whenever it ran, the file's outcome is
+ * *r.  XLZ_ERR_BAD_ARG: r is NULL, a NULL pointer with a length behind it.                                             */
+int xlz_bz2_decode_host(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, int verify, xlz_bz2_result *r);
+/* Many files as ONE batch into one caller-owned device buffer: one gathered upload of the file images; the block
+ * candidates of ALL files are one run of the symbol and the walk kernels (rounds of it when their scratch, about 6 bytes
+ * per block byte, exceeds xlz_ctx_set_bz2_scratch); after one small download the host settles every file's chain and the
+ * blocks' offsets; one launch expands the chain's blocks straight into the windows and one forms their CRCs over the
+ * destination.  Only statuses, lengths and digests leave the device.  Blocks above the launch-length cap, and every block
+ * in bz2 mode 2, are decoded on host threads and uploaded.  results[i] is what file i gets when it is passed alone; one bad
+ * file never fails the call, which returns XLZ_OK whenever it ran.  The call does not look at whether the bz2 mode is 0.
+ * XLZ_ERR_BAD_ARG, with nothing written: NULL arguments with n > 0; a file without a pointer to its length; a window that
+ * does not fit dst_cap, two windows that share a byte; d_dst is not device memory of the context's device.  n = 0 is
+ * XLZ_OK.  Nothing outside the files' windows is written.                                                             */
+int xlz_bz2_decode_many_device(xlz_ctx *ctx, const xlz_bz2_file *files, size_t n, void *d_dst, size_t dst_cap, int verify, xlz_bz2_result *results);
+/* The same into host memory: the windows lie back to back in one staging block of the context's pool, which comes down
+ * in ONE copy; only the good files are scattered into dst.                                                           */
+int xlz_bz2_decode_many(xlz_ctx *ctx, const xlz_bz2_file *files, size_t n, uint8_t *dst, size_t dst_cap, int verify, xlz_bz2_result *results);
+/* Of the most recent xlz_bz2_decode_many / xlz_bz2_decode_many_device on `ctx` that ran.                              */
+typedef struct xlz_bz2_stats {
+    uint64_t files, failed_files;
+    uint64_t candidates, chain_blocks, discarded_blocks; /* block magics; of them on a chain; decoded for nothing       */
+    uint64_t device_blocks, host_blocks;                 /* chain blocks expanded by the kernels; decoded on host threads */
+    uint64_t device_bytes, host_bytes;                   /* what they expanded to                                        */
+    uint32_t rounds, uploads;                            /* runs of the symbol and walk kernels; transfers of gathered inputs */
+    double symbols_ms, walk_ms, expand_ms, crc_ms;       /* the kernels' time by phase                                   */
+} xlz_bz2_stats;
+int xlz_ctx_last_bz2_stats(xlz_ctx *ctx, xlz_bz2_stats *out);
+/* 1: on the device (the default), 2: every block on host threads.  Mode 0 is accepted and means 1 to the many-calls.    */
+int xlz_ctx_set_bz2_mode(xlz_ctx *ctx, int mode);
+int xlz_ctx_bz2_mode(const xlz_ctx *ctx);
+/* The scratch one round of candidates may take, in bytes (0: the default, 6 GiB -- what the 1024 level-9 blocks take that
+ * a device of 256 CUs at four one-wave workgroups per CU has in flight at once).  A candidate's scratch always fits.    */
+int xlz_ctx_set_bz2_scratch(xlz_ctx *ctx, uint64_t bytes);
+/* Host only.  CRC-32/BZIP2 (polynomial 0x04C11DB7, not reflected) of `crc`'s bytes followed by p[0 .. n); crc = 0: of p. */
+uint32_t xlz_crc32_bzip2_host(uint32_t crc, const uint8_t *p, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

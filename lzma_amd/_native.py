@@ -70,6 +70,8 @@ EXPORTS = [
     "xlz_inflate_host", "xlz_inflate_batch", "xlz_ctx_set_deflate_mode", "xlz_ctx_deflate_mode", "xlz_ctx_last_inflate_stats",
     "xlz_adler32_device", "xlz_adler32_host", "xlz_adler32_combine",
     "xlz_gz_probe", "xlz_gz_decode_host", "xlz_gz_decode_many_device", "xlz_gz_decode_many", "xlz_ctx_last_gz_stats",
+    "xlz_bz2_probe", "xlz_bz2_decode_host", "xlz_bz2_decode_many_device", "xlz_bz2_decode_many", "xlz_ctx_last_bz2_stats",
+    "xlz_ctx_set_bz2_mode", "xlz_ctx_bz2_mode", "xlz_ctx_set_bz2_scratch", "xlz_crc32_bzip2_host",
 ]
 
 
@@ -287,6 +289,27 @@ class GzStats(ctypes.Structure):
                 ("device_items", ctypes.c_uint64), ("host_items", ctypes.c_uint64), ("crc_ranges", ctypes.c_uint64),
                 ("adler_ranges", ctypes.c_uint64), ("rounds", ctypes.c_uint32), ("uploads", ctypes.c_uint32),
                 ("adler_kernel_ms", ctypes.c_double)]
+
+
+class Bz2Info(ctypes.Structure):
+    _fields_ = [("level", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("candidates", ctypes.c_uint64), ("streams", ctypes.c_uint64),
+                ("size_hint", ctypes.c_uint64), ("size_bound", ctypes.c_uint64)]
+
+
+class Bz2File(ctypes.Structure):
+    _fields_ = [("inp", ctypes.c_void_p), ("in_len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("dst_cap", ctypes.c_uint64)]
+
+
+class Bz2Result(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("blocks", ctypes.c_uint32), ("out_len", ctypes.c_uint64), ("in_consumed", ctypes.c_uint64),
+                ("streams", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class Bz2Stats(ctypes.Structure):
+    _fields_ = [("files", ctypes.c_uint64), ("failed_files", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("chain_blocks", ctypes.c_uint64),
+                ("discarded_blocks", ctypes.c_uint64), ("device_blocks", ctypes.c_uint64), ("host_blocks", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64), ("host_bytes", ctypes.c_uint64), ("rounds", ctypes.c_uint32), ("uploads", ctypes.c_uint32),
+                ("symbols_ms", ctypes.c_double), ("walk_ms", ctypes.c_double), ("expand_ms", ctypes.c_double), ("crc_ms", ctypes.c_double)]
 
 
 class ZipEntry(ctypes.Structure):
@@ -579,6 +602,17 @@ def lib():
         L.xlz_gz_decode_many_device.argtypes = [vp, ctypes.POINTER(GzFile), sz, vp, sz, i32, ctypes.POINTER(GzResult)]
         L.xlz_gz_decode_many.argtypes = L.xlz_gz_decode_many_device.argtypes
         L.xlz_ctx_last_gz_stats.argtypes = [vp, ctypes.POINTER(GzStats)]
+    if hasattr(L, "xlz_bz2_probe"):  # (an older library loaded through XLZ_SO reads no .bz2)
+        L.xlz_bz2_probe.argtypes = [vp, sz, ctypes.POINTER(Bz2Info)]
+        L.xlz_bz2_decode_host.argtypes = [vp, sz, vp, sz, i32, ctypes.POINTER(Bz2Result)]
+        L.xlz_bz2_decode_many_device.argtypes = [vp, ctypes.POINTER(Bz2File), sz, vp, sz, i32, ctypes.POINTER(Bz2Result)]
+        L.xlz_bz2_decode_many.argtypes = L.xlz_bz2_decode_many_device.argtypes
+        L.xlz_ctx_last_bz2_stats.argtypes = [vp, ctypes.POINTER(Bz2Stats)]
+        L.xlz_ctx_set_bz2_mode.argtypes = [vp, i32]
+        L.xlz_ctx_bz2_mode.argtypes = [vp]
+        L.xlz_ctx_set_bz2_scratch.argtypes = [vp, ctypes.c_uint64]
+        L.xlz_crc32_bzip2_host.restype = ctypes.c_uint32
+        L.xlz_crc32_bzip2_host.argtypes = [ctypes.c_uint32, vp, sz]
     _lib = L
     return L
 

@@ -10,8 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libxlz.so")
-SOURCES = ["xlz_kernel.hip", "xlz_host.hip", "xlz_xz.hip", "xlz_7z.hip", "xlz_7z_extract.hip", "xlz_check_dev.hip", "xlz_filter_dev.hip", "xlz_sha256_dev.hip", "xlz_pack_dev.hip", "xlz_bcj2_dev.hip", "xlz_inflate_dev.hip", "xlz_tar_dev.hip", "xlz_zip.hip", "xlz_adler_dev.hip", "xlz_gz.hip"]
-HEADERS = ["xlz_format.h", "xlz_check.h", "xlz_check_dev.h", "xlz_check_host.h", "xlz_post.h", "xlz_xz_cover.h", "xlz_xz_many.h", "xlz_windows.h", "xlz_7z_files.h", "xlz_filter_dev.h", "xlz_sha256_dev.h", "xlz_pack_dev.h", "xlz_bcj2_dev.h", "xlz_inflate_dev.h", "xlz_tar_dev.h", "xlz_tar_walk.h", "xlz_zip.h", "xlz_adler_dev.h", "xlz_gz.h", "xlz_fastpath.inc", "xlz_fastpath_pb2.inc", "xlz_fastpath_pb2_br.inc", os.path.join("..", "..", "include", "xlz.h")]
+SOURCES = ["xlz_kernel.hip", "xlz_host.hip", "xlz_xz.hip", "xlz_7z.hip", "xlz_7z_extract.hip", "xlz_check_dev.hip", "xlz_filter_dev.hip", "xlz_sha256_dev.hip", "xlz_pack_dev.hip", "xlz_bcj2_dev.hip", "xlz_inflate_dev.hip", "xlz_tar_dev.hip", "xlz_zip.hip", "xlz_adler_dev.hip", "xlz_gz.hip", "xlz_bz2.hip"]
+HEADERS = ["xlz_format.h", "xlz_check.h", "xlz_check_dev.h", "xlz_check_host.h", "xlz_post.h", "xlz_xz_cover.h", "xlz_xz_many.h", "xlz_windows.h", "xlz_7z_files.h", "xlz_filter_dev.h", "xlz_sha256_dev.h", "xlz_pack_dev.h", "xlz_bcj2_dev.h", "xlz_inflate_dev.h", "xlz_tar_dev.h", "xlz_tar_walk.h", "xlz_zip.h", "xlz_adler_dev.h", "xlz_gz.h", "xlz_bz2_dev.h", "xlz_bz2.h", "xlz_fastpath.inc", "xlz_fastpath_pb2.inc", "xlz_fastpath_pb2_br.inc", os.path.join("..", "..", "include", "xlz.h")]
 ARCH = "gfx950"
 
 

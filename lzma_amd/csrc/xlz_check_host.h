@@ -25,6 +25,18 @@ void xlz_internal_7z_extract_stats_set(xlz_ctx *ctx, const xlz_7z_extract_stats 
 void xlz_internal_zip_extract_stats_set(xlz_ctx *ctx, const xlz_zip_extract_stats &s);
 // what xlz_ctx_last_gz_stats reports: set by every xlz_gz_decode_many / xlz_gz_decode_many_device that ran
 void xlz_internal_gz_stats_set(xlz_ctx *ctx, const xlz_gz_stats &s);
+// what xlz_ctx_last_bz2_stats reports: set by every xlz_bz2_decode_many / xlz_bz2_decode_many_device that ran
+void xlz_internal_bz2_stats_set(xlz_ctx *ctx, const xlz_bz2_stats &s);
+// what xlz_bz2.hip needs of the context: its device, its stream (void *: a hipStream_t), the bz2 mode and scratch budget
+struct Bz2Env {
+    int device, num_cus, mode;
+    void *stream;
+    uint64_t scratch;
+};
+int xlz_internal_bz2_env(xlz_ctx *ctx, Bz2Env *env);
+// the context's mutex, held around the device work of a round (not around the calls above and below, which take it)
+void xlz_internal_ctx_lock(xlz_ctx *ctx);
+void xlz_internal_ctx_unlock(xlz_ctx *ctx);
 // xlz_adler32_device behind its argument tests of the context and the pointer (the ranges lie inside buf_len); *ms
 // (optional) += the kernels' time
 int xlz_internal_adler_run(xlz_ctx *ctx, const void *d_buf, size_t buf_len, const xlz_adler_range *ranges, size_t n, uint32_t *digests, double *ms);

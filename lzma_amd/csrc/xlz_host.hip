@@ -268,6 +268,10 @@ struct xlz_ctx {
     // raw deflate streams (xlz_inflate_dev.hip): xlz_ctx_set_deflate_mode, xlz_ctx_last_inflate_stats
     int deflate_mode = 0;
     xlz_inflate_stats last_inflate = {};
+    // .bz2 files (xlz_bz2.hip): xlz_ctx_set_bz2_mode, xlz_ctx_set_bz2_scratch, xlz_ctx_last_bz2_stats
+    int bz2_mode = 0;
+    uint64_t bz2_scratch = 0;
+    xlz_bz2_stats last_bz2 = {};
 };
 
 // Scratch of one kind of post-decode kernel of a batch: device and pinned memory from where the batch's memory comes
@@ -2994,6 +2998,28 @@ extern "C" int xlz_inflate_batch(xlz_ctx *ctx, const xlz_inflate_item *items, si
 extern "C" int xlz_ctx_set_deflate_mode(xlz_ctx *ctx, int mode) { return set_mode(ctx, &xlz_ctx::deflate_mode, mode, 2); }
 extern "C" int xlz_ctx_deflate_mode(const xlz_ctx *ctx) { return ctx ? ctx->deflate_mode : XLZ_ERR_BAD_ARG; }
 extern "C" int xlz_ctx_last_inflate_stats(xlz_ctx *ctx, xlz_inflate_stats *out) { return last_stats(ctx, &xlz_ctx::last_inflate, out); }
+
+// .bz2 files as one batch (xlz_bz2.hip)
+extern "C" int xlz_ctx_set_bz2_mode(xlz_ctx *ctx, int mode) { return set_mode(ctx, &xlz_ctx::bz2_mode, mode, 2); }
+extern "C" int xlz_ctx_bz2_mode(const xlz_ctx *ctx) { return ctx ? ctx->bz2_mode : XLZ_ERR_BAD_ARG; }
+extern "C" int xlz_ctx_set_bz2_scratch(xlz_ctx *ctx, uint64_t bytes)
+{
+    if (!ctx) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    ctx->bz2_scratch = bytes;
+    return XLZ_OK;
+}
+extern "C" int xlz_ctx_last_bz2_stats(xlz_ctx *ctx, xlz_bz2_stats *out) { return last_stats(ctx, &xlz_ctx::last_bz2, out); }
+void xlz_internal_bz2_stats_set(xlz_ctx *ctx, const xlz_bz2_stats &s) { publish(ctx, &xlz_ctx::last_bz2, s); }
+void xlz_internal_ctx_lock(xlz_ctx *ctx) { ctx->mu.lock(); }
+void xlz_internal_ctx_unlock(xlz_ctx *ctx) { ctx->mu.unlock(); }
+int xlz_internal_bz2_env(xlz_ctx *ctx, Bz2Env *env)
+{
+    if (!ctx || !env) return XLZ_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    env->device = ctx->device, env->num_cus = ctx->num_cus, env->stream = ctx->stream, env->mode = ctx->bz2_mode, env->scratch = ctx->bz2_scratch;
+    return XLZ_OK;
+}
 
 int xlz_internal_device_block(xlz_ctx *ctx, size_t bytes, void **p)
 {
